@@ -8,8 +8,10 @@ halo refresh of uc, vc, divg_d (periodic copy on one GPU, RCCL peer exchange acr
 rank owns a 384 x 384 x 127 block of a (384*px) x (384*py) doubly periodic domain (weak scaling).
 metric: cell-updates/s, one cell-update = one (i,j,k) cell through one c_sw+d_sw pair.
 
-Prints ONE JSON line (see the build contract): value, roofline (HIP-event timed dominant kernel
-against its algorithmic bytes), cpu_baseline (the oracle port on the host cores, bounded sample).
+Prints ONE JSON line (see the build contract): value and ms_per_step of the `--steps` timed steps.  A plain run
+does only that (set up, warm up, time, --dump-outputs); --full adds the other legs: roofline (HIP-event timed dominant
+kernel against its algorithmic bytes), the general-metrics pair, the strong-scaling domain, the model step, the cubed
+sphere and cpu_baseline (the oracle port on the host cores, bounded sample).
 """
 import argparse
 import json
@@ -49,6 +51,30 @@ PAIR_ALG_BYTES_DCON0 = 320.0 # ... with d_con = 0 (the flags this bench runs): h
 SPINUP = int(os.environ.get("FV3_BENCH_SPINUP", "0"))
 DRYRUN = os.environ.get("FV3_BENCH_DRYRUN") == "1"   # see main()
 DEV = "cpu" if DRYRUN else "cuda"
+
+
+DUMP_POINTS = 1 << 17   # --dump-outputs: values kept per array (1 MB in fp64; a step's 23 to 25 arrays stay well under 64 MB)
+DUMP_SEED = 20261016
+# what d_sw writes besides c_sw's outputs (CSW_OUT) and their stagger: the flux / Courant accumulators, the updated state, and
+# heat_s / diss_e (written only when a level has d_con > 0)
+DSW_OUT = (("mfx", "FX"), ("mfy", "FY"), ("cx", "CX"), ("cy", "CY"), ("crx", "CX"), ("cry", "CY"), ("xfx", "CX"), ("yfx", "CY"),
+           ("delp_out", "A"), ("pt_out", "A"), ("u_out", "U"), ("v_out", "V"), ("w_out", "A"), ("heat_s", "CC"), ("diss_e", "CC"))
+
+
+def dump_outputs(dirname, fields, bd):
+    """--dump-outputs: fields = {name: (device array, stagger kind)}, every array the timed step hands its caller, written as
+    DIR/<name>.npy in float64 on the compute domain of bd (is..ie, js..je, one more point where the kind is staggered; every k).
+    A compute domain of more than DUMP_POINTS values is sampled at DUMP_POINTS fixed points (seeded: the same points on every run
+    with the same arguments), flattened in Fortran order."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, (arr, kind) in fields.items():
+        ilo, ihi, jlo, jhi = bd.limits(kind)
+        di, dj = int(ihi in (bd.ie + 1, bd.ied + 1)), int(jhi in (bd.je + 1, bd.jed + 1))
+        a = arr.download()[bd.is_ - ilo:bd.ie + di - ilo + 1, bd.js - jlo:bd.je + dj - jlo + 1, :]
+        if a.size > DUMP_POINTS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_POINTS, replace=False))
+            a = a.ravel(order="F")[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def level_sets(lev, sponge_march=False):
@@ -91,6 +117,11 @@ def parse():
     ap.add_argument("--general-metrics", action="store_true",
                     help="FV3_MI355X_GEOM=0: read every metric row (what a cubed-sphere gridstruct needs) instead of "
                          "using the uniform-Cartesian kernels the library selects for this doubly periodic gridstruct")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other leg: roofline, general metrics, strong scaling, model step, cubed "
+                         "sphere, cpu_baseline (the --no-* options switch single legs off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; rank 0's block)")
     a = ap.parse_args()
     a.parity_columns = True   # the library has one mode of the column solvers (the tolerance mode of rounds 2 - 4 was removed in round 5)
     return a
@@ -328,9 +359,7 @@ def cubed_sphere_leg(a, torch, stream):
     st = smooth_state(Bounds(1, nx, 1, nx), npz, noise=0.05)
     d = {k: ctx.from_host(v) for k, v in st.items()}
     del st
-    for n, kind in tuple(CSW_OUT) + (("mfx", "FX"), ("mfy", "FY"), ("cx", "CX"), ("cy", "CY"), ("crx", "CX"), ("cry", "CY"),
-                                    ("xfx", "CX"), ("yfx", "CY"), ("delp_out", "A"), ("pt_out", "A"), ("u_out", "U"), ("v_out", "V"),
-                                    ("w_out", "A"), ("heat_s", "CC"), ("diss_e", "CC")):
+    for n, kind in CSW_OUT + DSW_OUT:
         d[n] = ctx.zeros(kind, npz)
     ctx.dsw_levels(level_coefficients(npz, DynFlags()))
     dt = 22.5
@@ -508,9 +537,7 @@ def cubed_six_ranks(a, torch, dist, rank, json_fd):
     st = smooth_state(Bounds(1, nx, 1, nx), npz, noise=0.05)
     d = {k: ctx.from_host(v) for k, v in st.items()}
     del st
-    for n, kind in tuple(CSW_OUT) + (("mfx", "FX"), ("mfy", "FY"), ("cx", "CX"), ("cy", "CY"), ("crx", "CX"), ("cry", "CY"),
-                                    ("xfx", "CX"), ("yfx", "CY"), ("delp_out", "A"), ("pt_out", "A"), ("u_out", "U"), ("v_out", "V"),
-                                    ("w_out", "A"), ("heat_s", "CC"), ("diss_e", "CC")):
+    for n, kind in CSW_OUT + DSW_OUT:
         d[n] = ctx.zeros(kind, npz)
     ctx.dsw_levels(level_coefficients(npz, DynFlags()))
     dt = 22.5
@@ -538,6 +565,8 @@ def cubed_six_ranks(a, torch, dist, rank, json_fd):
         step()
     fence()
     el = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {n: (d[n], kind) for n, kind in CSW_OUT + DSW_OUT}, g.bd)
     t = torch.tensor([el], dtype=torch.float64, device=DEV)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t.item())
@@ -558,41 +587,43 @@ def cubed_six_ranks(a, torch, dist, rank, json_fd):
     if DRYRUN:
         out["dry_run"] = "FV3_BENCH_DRYRUN=1: host logic harness + gloo, no GPU -- plumbing only, the numbers mean nothing"
     del d
-    try:        # whole model steps: BASELINE configs[2] with one face per GPU
-        ak, bk, _, _ = set_eta(npz) if npz in (79, 127) else (None, None, None, None)
-        if ak is None:
-            sig = np.linspace(0.0, 1.0, npz + 1) ** 1.5
-            ak, bk = 300.0 * (1.0 - sig), sig.copy()
-        st = jablonowski_williamson(cs, ak, bk, hydrostatic=False)
-        cs.topo.update("A", [s_["phis"] for s_ in st])
-        s_ = st[rank]
-        k_split, n_split, dt_atmos = 2, 5, 225.0
-        fl = DynFlags(n_split=n_split, hydrostatic=False, ptop=float(ak[0]))
-        ng = g.bd.ng
-        c = (slice(ng, ng + nx), slice(ng, ng + nx))
-        pkz = ((-fl.rdgas / fl.grav) * s_["delp"][c] * s_["pt"][c] / s_["delz"]) ** fl.akap
-        s_["pt"][c] = s_["pt"][c] / pkz
-        fv = FvDynamics(ctx, fl, ak, bk, nq=0, k_split=k_split, halo=halo, dist=dist)
-        fv.dc.set_state(s_["u"], s_["v"], s_["w"], s_["delp"], s_["pt"], s_["delz"], s_["phis"])
-        del st
-        fv.step(dt_atmos)
-        fence()
-        nrep = 3
-        t0 = time.perf_counter()
-        for _ in range(nrep):
+    out["sphere_six_gpus"] = None
+    if a.full:
+        try:        # whole model steps: BASELINE configs[2] with one face per GPU
+            ak, bk, _, _ = set_eta(npz) if npz in (79, 127) else (None, None, None, None)
+            if ak is None:
+                sig = np.linspace(0.0, 1.0, npz + 1) ** 1.5
+                ak, bk = 300.0 * (1.0 - sig), sig.copy()
+            st = jablonowski_williamson(cs, ak, bk, hydrostatic=False)
+            cs.topo.update("A", [s_["phis"] for s_ in st])
+            s_ = st[rank]
+            k_split, n_split, dt_atmos = 2, 5, 225.0
+            fl = DynFlags(n_split=n_split, hydrostatic=False, ptop=float(ak[0]))
+            ng = g.bd.ng
+            c = (slice(ng, ng + nx), slice(ng, ng + nx))
+            pkz = ((-fl.rdgas / fl.grav) * s_["delp"][c] * s_["pt"][c] / s_["delz"]) ** fl.akap
+            s_["pt"][c] = s_["pt"][c] / pkz
+            fv = FvDynamics(ctx, fl, ak, bk, nq=0, k_split=k_split, halo=halo, dist=dist)
+            fv.dc.set_state(s_["u"], s_["v"], s_["w"], s_["delp"], s_["pt"], s_["delz"], s_["phis"])
+            del st
             fv.step(dt_atmos)
-        fence()
-        wall = (time.perf_counter() - t0) / nrep
-        t = torch.tensor([wall], dtype=torch.float64, device=DEV)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        wall = float(t.item())
-        out["sphere_six_gpus"] = {"grid": f"C{nx} L{npz}", "sypd": dt_atmos / (365.0 * wall), "wall_s_per_dt_atmos": wall,
-                                  "dt_atmos_s": dt_atmos, "k_split": k_split, "n_split": n_split,
-                                  "whole_step": whole_step_roofline(cells, wall, k_split * n_split, k_split, 0),
-                                  "column_solvers": "parity kernels",
-                                  "finite": bool(np.isfinite(fv.dc.d["delp"].download()[c]).all())}
-    except Exception as e:  # noqa: BLE001
-        out["sphere_six_gpus"] = {"error": f"{type(e).__name__}: {e}"}
+            fence()
+            nrep = 3
+            t0 = time.perf_counter()
+            for _ in range(nrep):
+                fv.step(dt_atmos)
+            fence()
+            wall = (time.perf_counter() - t0) / nrep
+            t = torch.tensor([wall], dtype=torch.float64, device=DEV)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            wall = float(t.item())
+            out["sphere_six_gpus"] = {"grid": f"C{nx} L{npz}", "sypd": dt_atmos / (365.0 * wall), "wall_s_per_dt_atmos": wall,
+                                      "dt_atmos_s": dt_atmos, "k_split": k_split, "n_split": n_split,
+                                      "whole_step": whole_step_roofline(cells, wall, k_split * n_split, k_split, 0),
+                                      "column_solvers": "parity kernels",
+                                      "finite": bool(np.isfinite(fv.dc.d["delp"].download()[c]).all())}
+        except Exception as e:  # noqa: BLE001
+            out["sphere_six_gpus"] = {"error": f"{type(e).__name__}: {e}"}
     ctx.close()
     if rank == 0:
         os.write(json_fd, (json.dumps(out) + "\n").encode())
@@ -712,11 +743,7 @@ def main():
         st = smooth_state(Bounds(1, nxb, 1, nyb), npz, noise=0.05)  # same synthetic block on every rank
         d = {k: ctx.from_host(v) for k, v in st.items()}
         del st
-        for n, kind in CSW_OUT:
-            d[n] = ctx.zeros(kind, npz)
-        for n, kind in (("mfx", "FX"), ("mfy", "FY"), ("cx", "CX"), ("cy", "CY"), ("crx", "CX"), ("cry", "CY"),
-                        ("xfx", "CX"), ("yfx", "CY"), ("delp_out", "A"), ("pt_out", "A"), ("u_out", "U"),
-                        ("v_out", "V"), ("w_out", "A"), ("heat_s", "CC"), ("diss_e", "CC")):
+        for n, kind in CSW_OUT + DSW_OUT:
             d[n] = ctx.zeros(kind, npz)
         ctx.dsw_levels(lev)
         heating = bool(np.any(np.asarray(lev["d_con_k"]) > 1.0e-5))
@@ -744,11 +771,13 @@ def main():
                 ctx.d_sw(*dsw_args)
 
         step.block = (nxb, nyb)
+        step.outputs = {n: (d[n], kind) for n, kind in CSW_OUT + DSW_OUT if heating or n not in ("heat_s", "diss_e")}
         return ctx, d, step
 
-    def run(ctx, d, step, steps, warmup):
-        """`warmup` untimed and EXACTLY `steps` timed passes of c_sw -> halo -> d_sw on the resident state, then a profiled pass (HIP
-        events around every launch on its own stream) for the per-launch roofline."""
+    def run(ctx, d, step, steps, warmup, profile=True, dump_dir=None):
+        """`warmup` untimed and EXACTLY `steps` timed passes of c_sw -> halo -> d_sw on the resident state; dump_dir: what the last
+        timed pass computed -> dump_dir/<name>.npy; profile: then a profiled pass (HIP events around every launch on its own stream)
+        for the per-launch roofline."""
         geom = ctx.geom
         nprof = 10
         nxb, nyb = step.block
@@ -764,16 +793,20 @@ def main():
             tstep()
         fence()
         el = time.perf_counter() - t0
+        if dump_dir and rank == 0:     # before the profiled passes: d_sw accumulates into mfx, mfy, cx, cy
+            dump_outputs(dump_dir, step.outputs, Bounds(1, nxb, 1, nyb))
         # the profiled pass (HIP events around every launch, on the launch stream) AFTER the timed region: the same warm GPU -- in
         # round 4 it ran first, on the idle clocks of a fresh process, and priced the kernels 15-20 % slower than the timed steps ran
-        ctx.profile(True)
-        for _ in range(2):
-            step()
-        ctx.profile_report()
-        for _ in range(nprof):
-            step()
-        rep = ctx.profile_report()
-        ctx.profile(False)
+        rep = {}
+        if profile:
+            ctx.profile(True)
+            for _ in range(2):
+                step()
+            ctx.profile_report()
+            for _ in range(nprof):
+                step()
+            rep = ctx.profile_report()
+            ctx.profile(False)
         if world > 1:
             t = torch.tensor([el], dtype=torch.float64, device=DEV)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -825,7 +858,7 @@ def main():
     # cubed-sphere-representative pair (every metric row read, geometry mode 0), then the headline measurement
     main_set = setup(a.general_metrics)
     gm = None
-    if not a.general_metrics and not a.no_general:
+    if a.full and not a.general_metrics and not a.no_general:
         try:
             gen_set = setup(True)
             gsteps = max(10, a.steps // 2)
@@ -835,7 +868,7 @@ def main():
             del gen_set
         except Exception as e:  # noqa: BLE001
             gm = {"error": f"{type(e).__name__}: {e}"}
-    m = run(*main_set, a.steps, a.warmup)
+    m = run(*main_set, a.steps, a.warmup, profile=a.full, dump_dir=a.dump_outputs)
     del main_set
     el, value, finite, roof, geom = m["el"], m["value"], m["finite"], m["roof"], m["geom"]
 
@@ -859,7 +892,7 @@ def main():
     # a failure is reported, not raised -- but it must fail on all ranks alike, so the checks are on values every rank shares.
     out["strong_scaling"] = None
     sd = a.strong_domain if a.strong_domain is not None else (0 if DRYRUN else 1024)   # (the dry run's host harness takes seconds per 16^2 step)
-    if not a.domain and sd and not a.general_metrics:
+    if a.full and not a.domain and sd and not a.general_metrics:
         if sd % px or sd % py:
             out["strong_scaling"] = {"error": f"{sd} does not divide over the {px} x {py} layout"}
         else:
@@ -884,7 +917,7 @@ def main():
     # the secondary legs must never cost the headline line: a failure there is reported, not raised
     out["model_step"] = None
     # N > 1: the SYPD leg is off unless asked for (a failure on one rank would leave the others in a collective)
-    if not a.no_model_step and (world == 1 or a.model_step_multi):
+    if a.full and not a.no_model_step and (world == 1 or a.model_step_multi):
         try:
             # the SYPD is quoted with the library's one mode of the column kernels (north_star's 1e-12 on whole steps holds by
             # construction: bit-comparable with the oracle)
@@ -893,7 +926,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["model_step"] = {"error": f"{type(e).__name__}: {e}"}
     out["cubed_sphere"] = None
-    if world == 1 and not a.no_cubed:
+    if a.full and world == 1 and not a.no_cubed:
         try:
             out["cubed_sphere"] = cubed_sphere_leg(a, torch, stream)
         except Exception as e:  # noqa: BLE001
@@ -904,7 +937,7 @@ def main():
         out["pair_one_gnomonic_c384_face_ms"] = cs["pair_one_face"].get("ms")
     if isinstance(cs.get("sphere_one_gpu"), dict):
         out["c384_sphere_one_gpu_sypd"] = cs["sphere_one_gpu"].get("sypd")
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu:
         try:
             out["cpu_baseline"] = cpu_baseline(nx, a.cpu_seconds)
         except Exception as e:  # noqa: BLE001

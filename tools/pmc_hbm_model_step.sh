@@ -6,7 +6,7 @@ TAG=${1:-vX}
 R=$PWD
 mkdir -p gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --no-cpu --steps 2 --warmup 1"
+CMD="python $R/bench.py --full --no-cpu --steps 2 --warmup 1"
 timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/pf -- $CMD > /tmp/pf.log 2>&1
 timeout 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d /tmp/pw -- $CMD > /tmp/pw.log 2>&1
 timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/pk -- $CMD > /tmp/pk.log 2>&1

@@ -6,8 +6,8 @@ TAG=${1:-vX}
 R=$PWD
 mkdir -p gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace -d /tmp/pl1 -- python $R/bench.py --no-cpu --steps 2 --warmup 1 > /tmp/pl1.log 2>&1
-timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/pl2 -- python $R/bench.py --no-cpu --steps 2 --warmup 1 > /tmp/pl2.log 2>&1
+timeout 900 rocprofv3 --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace -d /tmp/pl1 -- python $R/bench.py --full --no-cpu --steps 2 --warmup 1 > /tmp/pl1.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/pl2 -- python $R/bench.py --full --no-cpu --steps 2 --warmup 1 > /tmp/pl2.log 2>&1
 cd $R
 python - > gpurun_out/$TAG/pmc_l1.csv <<'PY'
 import glob, sqlite3, collections

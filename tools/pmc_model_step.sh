@@ -4,7 +4,7 @@ TAG=${1:-vX}
 R=$PWD
 mkdir -p gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_INSTS_VMEM GRBM_GUI_ACTIVE --kernel-trace -d /tmp/pm -- python $R/bench.py --no-cpu --steps 2 --warmup 1 > /tmp/pm.log 2>&1
+timeout 900 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_INSTS_VMEM GRBM_GUI_ACTIVE --kernel-trace -d /tmp/pm -- python $R/bench.py --full --no-cpu --steps 2 --warmup 1 > /tmp/pm.log 2>&1
 cd $R
 DB=$(find /tmp/pm -name "*_results.db" | head -1)
 python - "$DB" > gpurun_out/$TAG/pmc_sq_model_step.csv <<'PY'

@@ -5,14 +5,15 @@
 TAG=${1:-vX}
 R=$PWD
 mkdir -p gpurun_out/$TAG
+OUT=$_      # the tag's output directory, made on the line above
 bash tools/pmc_hbm_pair.sh $TAG
 bash tools/pmc_remap.sh $TAG
 bash tools/pmc_riem.sh $TAG      # round 6: the Riemann solvers' counters every round (none were taken in round 5)
 cp gpurun_out/$TAG/hbm_traffic.json profiles/hbm_traffic.json
 cp gpurun_out/$TAG/hbm_traffic_remap.json profiles/hbm_traffic_remap.json
-python bench.py > gpurun_out/$TAG/bench.json 2> gpurun_out/$TAG/bench.err
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt -- python $R/bench.py --no-cpu --no-model-step > /tmp/kt.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt -- python $R/bench.py --full --no-cpu --no-model-step > /tmp/kt.log 2>&1
 cd $R
 DB=$(find /tmp/kt -name "*_results.db" | head -1)
 python - $DB > gpurun_out/$TAG/kernel_stats.csv <<'PY'

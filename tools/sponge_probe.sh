@@ -1,7 +1,7 @@
 #!/bin/bash
 # what the two sponge levels (LDS-tile kernels on the side stream) cost the pair: headline / no sponge / serialised
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; out=gpurun_out/${1:-sponge}; mkdir -p $out
-F="--no-cpu --no-model-step --no-cubed --no-general --steps 100 --warmup 20"
+F="--full --no-cpu --no-model-step --no-cubed --no-general --steps 100 --warmup 20"
 for r in 1 2; do
 python bench.py $F > $out/base_$r.json 2> $out/base_$r.err
 FV3_BENCH_SPONGE=0 python bench.py $F > $out/nosponge_$r.json 2> $out/nosponge_$r.err

@@ -1,7 +1,7 @@
 #!/bin/bash
 # grouped row steps of the fused transport kernel (FV3_UNROLL_T): variants built into gpurun_in/*.so against the shipped library
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; out=gpurun_out/${1:-unroll}; mkdir -p $out
-F="--no-cpu --no-model-step --no-cubed --no-general --steps 100 --warmup 20"
+F="--full --no-cpu --no-model-step --no-cubed --no-general --steps 100 --warmup 20"
 for r in 1 2; do
 python bench.py $F > $out/base_$r.json 2>/dev/null
 for v in gpurun_in/*.so; do n=$(basename $v .so); FV3_MI355X_SO=$PWD/$v python bench.py $F > $out/${n}_$r.json 2>/dev/null; done
