@@ -309,7 +309,8 @@ struct DswCubedD4 {
 // W(m), DX(m), RDX(m): the wind, its metric and the reciprocal along the line; i: the corner index along the line; c: the
 // advective displacement there; edge_row: the line runs along a face edge.
 template <class W, class DX, class RDX>
-FV3_HD double tp_wind_face_cs(const W &w, const DX &dx, const RDX &rdx, int i, double c, int iord, int npx, bool edge_row) {
+FV3_HD double tp_wind_face_cs(const W &w, const DX &dx, const RDX &rdx, int i, double c, int iord, int npx, bool edge_row,
+                              double lim_fac) {
   constexpr double r3 = 1. / 3., near_zero = 1.E-9, p1 = 7. / 12., p2 = -1. / 12.;
   constexpr double c1 = -2. / 14., c2 = 11. / 14., c3 = 5. / 14., s11 = 11. / 14., s14 = 4. / 7., s15 = 3. / 14.;
   const int ic = (c > 0.) ? i - 1 : i;
@@ -388,7 +389,7 @@ FV3_HD double tp_wind_face_cs(const W &w, const DX &dx, const RDX &rdx, int i, d
     const double cfl = c * rdx(i);
     return w0 + (1. + cfl) * (bl + cfl * (bl + br));
   }
-  // iord = 5, 6, 7 (:2187-2377)
+  // iord = 1 .. 7 (:2187-2377): the edge overrides of bl / br (:2200-2239) serve all of them
   auto al = [&](int m) { return p1 * (w(m - 1) + w(m)) + p2 * (w(m - 2) + w(m + 1)); };
   auto x_edge = [&](int e) {
     return 0.5 * (((2. * dx(e - 1) + dx(e - 2)) * (w(e - 1)) - dx(e - 1) * w(e - 2)) / (dx(e - 1) + dx(e - 2)) +
@@ -433,6 +434,7 @@ FV3_HD double tp_wind_face_cs(const W &w, const DX &dx, const RDX &rdx, int i, d
   double blm, brm, bl0, br0;
   cell(i - 1, blm, brm);
   cell(i, bl0, br0);
+  if (iord <= 4) return ppm_flux_sw_lin(iord, blm, brm, bl0, br0, w(i - 1), w(i), c, rdx(i - 1), rdx(i), lim_fac);
   const double b0m = blm + brm, b00 = bl0 + br0;
   auto edge_cell = [&](int m) { return m == 0 || m == 1 || m == npx - 1 || m == npx; };
   bool sm, s0;
@@ -485,11 +487,11 @@ struct DswCubedD5 {
     auto wv = [&](int m) { return v(i, m, k); };
     auto dyv = [&](int m) { return g.dy[g.iV(i, m)]; };
     auto rdyv = [&](int m) { return g.rdy[g.iV(i, m)]; };
-    const double ubn = tp_wind_face_cs(wv, dyv, rdyv, j, vb, s.a.hord_mt, npy, i == 1 || i == npx);
+    const double ubn = tp_wind_face_cs(wv, dyv, rdyv, j, vb, s.a.hord_mt, npy, i == 1 || i == npx, g.lim_fac);
     auto wu = [&](int m) { return u(m, j, k); };
     auto dxu = [&](int m) { return g.dx[g.iU(m, j)]; };
     auto rdxu = [&](int m) { return g.rdx[g.iU(m, j)]; };
-    const double vbn = tp_wind_face_cs(wu, dxu, rdxu, i, ub, s.a.hord_mt, npx, j == 1 || j == npy);
+    const double vbn = tp_wind_face_cs(wu, dxu, rdxu, i, ub, s.a.hord_mt, npx, j == 1 || j == npy, g.lim_fac);
     double ke = vb * ubn;
     ke = 0.5 * (ke + ub * vbn);
     const double dt6 = dt / 6.;

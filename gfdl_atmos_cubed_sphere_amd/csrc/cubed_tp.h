@@ -127,7 +127,7 @@ FV3_HD void ppm_cell_mono_cs(const Q &q, const D &d, int ic, int iord, int npx, 
 
 // face value at face i of a line (between cells i-1 and i) with Courant number c; Q / D: accessors of the line
 template <class Q, class D>
-FV3_HD double ppm_face_cs(const Q &q, const D &d, int i, double c, int iord, int npx) {
+FV3_HD double ppm_face_cs(const Q &q, const D &d, int i, double c, int iord, int npx, double lim_fac) {
   constexpr double r12 = 1. / 12., p1 = 7. / 12., p2 = -1. / 12., c1 = -2. / 14., c2 = 11. / 14., c3 = 5. / 14.;
   if (iord == 7) {  // :685-699: both cells of the face, the flux form of the unlimited family
     double blm, brm, bl0, br0;
@@ -153,7 +153,7 @@ FV3_HD double ppm_face_cs(const Q &q, const D &d, int i, double c, int iord, int
     if (c > 0.) return q0 + (1. - c) * (br - c * (bl + br));
     return q0 + (1. + c) * (bl + c * (bl + br));
   }
-  // iord = 5, -5, 6 (:365-560)
+  // iord = +-1 .. +-4, 5, -5, +-6 (:365-560): the edge values of al (:373-386) serve all of them and are clamped too
   auto al = [&](int m) {
     double a;
     if (m == 0 || m == npx - 1)
@@ -168,11 +168,12 @@ FV3_HD double ppm_face_cs(const Q &q, const D &d, int i, double c, int iord, int
   };
   const double alm = al(i - 1), al0 = al(i), alp = al(i + 1);
   const double qm1 = q(i - 1), q0 = q(i);
+  if (iord >= -4 && iord <= 4) return ppm_flux_lin(iord < 0 ? -iord : iord, alm, al0, alp, qm1, q0, c, lim_fac);
   const double blm = alm - qm1, brm = al0 - qm1, b0m = blm + brm;
   const double bl0 = al0 - q0, br0 = alp - q0, b00 = bl0 + br0;
   auto edge_cell = [&](int m) { return m == 0 || m == 1 || m == npx - 1 || m == npx; };
   bool sm, s0;
-  if (iord == 6) {
+  if (iord == 6 || iord == -6) {  // the edge fix of the flag (:534-546) is theirs alone among the orders below 5
     sm = edge_cell(i - 1) ? (blm * brm < 0.) : (3. * fabs(b0m) < fabs(blm - brm));  // :534-546
     s0 = edge_cell(i) ? (bl0 * br0 < 0.) : (3. * fabs(b00) < fabs(bl0 - br0));
   } else {
@@ -233,12 +234,12 @@ struct Tp2dCubedT1 {
     if (j >= g.js && j <= g.je + 1) {
       auto ql = [&](int m) { int ii = i, jj = m; copyc_src(2, npx, npy, ii, jj); return q(ii, jj, k); };
       auto dl = [&](int m) { return FV3_M(dya, i, m); };
-      view_A(g, s.fy2)(i, j, k) = ppm_face_cs(ql, dl, j, cview_CY(g, s.cry)(i, j, k), ord_in, npy);
+      view_A(g, s.fy2)(i, j, k) = ppm_face_cs(ql, dl, j, cview_CY(g, s.cry)(i, j, k), ord_in, npy, g.lim_fac);
     }
     if (i >= g.is && i <= g.ie + 1) {
       auto ql = [&](int m) { int ii = m, jj = j; copyc_src(1, npx, npy, ii, jj); return q(ii, jj, k); };
       auto dl = [&](int m) { return FV3_M(dxa, m, j); };
-      view_A(g, s.fx2)(i, j, k) = ppm_face_cs(ql, dl, i, cview_CX(g, s.crx)(i, j, k), ord_in, npx);
+      view_A(g, s.fx2)(i, j, k) = ppm_face_cs(ql, dl, i, cview_CX(g, s.crx)(i, j, k), ord_in, npx, g.lim_fac);
     }
   }
 };
@@ -275,14 +276,14 @@ struct Tp2dCubedT3 {
     if (j <= g.je) {
       auto ql = [&](int m) { return qi(m, j, k); };
       auto dl = [&](int m) { return FV3_M(dxa, m, j); };
-      const double f = ppm_face_cs(ql, dl, i, cview_CX(g, s.crx)(i, j, k), s.hord, g.npx);
+      const double f = ppm_face_cs(ql, dl, i, cview_CX(g, s.crx)(i, j, k), s.hord, g.npx, g.lim_fac);
       const double m = s.mfx ? cview_FX(g, s.mfx)(i, j, k) : cview_CX(g, s.xfx)(i, j, k);
       view_FX(g, s.fx)(i, j, k) = 0.5 * (f + fx2(i, j, k)) * m;
     }
     if (i <= g.ie) {
       auto ql = [&](int m) { return qj(i, m, k); };
       auto dl = [&](int m) { return FV3_M(dya, i, m); };
-      const double f = ppm_face_cs(ql, dl, j, cview_CY(g, s.cry)(i, j, k), s.hord, g.npy);
+      const double f = ppm_face_cs(ql, dl, j, cview_CY(g, s.cry)(i, j, k), s.hord, g.npy, g.lim_fac);
       const double m = s.mfy ? cview_FY(g, s.mfy)(i, j, k) : cview_CY(g, s.yfx)(i, j, k);
       view_FY(g, s.fy)(i, j, k) = 0.5 * (f + fy2(i, j, k)) * m;
     }

@@ -96,7 +96,7 @@ struct Tp2dFrameFused {
           const int i = xa + idx % nx_, j = ya + idx / nx_;
           auto ql = [&](int m) { return TF(qx, m, j); };
           auto dl = [&](int m) { return FV3_M(dxa, m, j); };
-          TF(fx2, i, j) = ppm_face_cs(ql, dl, i, cx(i, j, k), ord_in, npx);
+          TF(fx2, i, j) = ppm_face_cs(ql, dl, i, cx(i, j, k), ord_in, npx, g.lim_fac);
         }
         // fy2(i, j): i in [ia - 3, ib + 2], j in [ja, jb + 1], inside (isd:ied, js:je+1)
         const int ua = (ia - 3 > g.isd) ? ia - 3 : g.isd, ub = (ib + 2 < g.ied) ? ib + 2 : g.ied, va = ja, vb = (jb + 1 < g.je + 1) ? jb + 1 : g.je + 1;
@@ -105,7 +105,7 @@ struct Tp2dFrameFused {
           const int i = ua + idx % nu, j = va + idx / nu;
           auto ql = [&](int m) { return TF(qy, i, m); };
           auto dl = [&](int m) { return FV3_M(dya, i, m); };
-          TF(fy2, i, j) = ppm_face_cs(ql, dl, j, cy(i, j, k), ord_in, npy);
+          TF(fy2, i, j) = ppm_face_cs(ql, dl, j, cy(i, j, k), ord_in, npy, g.lim_fac);
         }
       }
       FV3_SYNC_LDS();
@@ -137,7 +137,7 @@ struct Tp2dFrameFused {
           if (j <= g.je) {
             auto ql = [&](int m) { return TF(qi, m, j); };
             auto dl = [&](int m) { return FV3_M(dxa, m, j); };
-            const double fo = ppm_face_cs(ql, dl, i, cx(i, j, k), hord, npx);
+            const double fo = ppm_face_cs(ql, dl, i, cx(i, j, k), hord, npx, g.lim_fac);
             const double m = emfx ? cview_FX(g, emfx)(i, j, k) : ((n == 0) ? xf(i, j, k) : TF(mfx, i, j));
             double v = 0.5 * (fo + TF(fx2, i, j)) * m;
             if (n == 0 && dfx && dcoef[k] > 1.E-4) v = v + cview_V(g, dfx)(i, j, k);
@@ -147,7 +147,7 @@ struct Tp2dFrameFused {
           if (i <= g.ie) {
             auto ql = [&](int m) { return TF(qj, i, m); };
             auto dl = [&](int m) { return FV3_M(dya, i, m); };
-            const double fo = ppm_face_cs(ql, dl, j, cy(i, j, k), hord, npy);
+            const double fo = ppm_face_cs(ql, dl, j, cy(i, j, k), hord, npy, g.lim_fac);
             const double m = emfy ? cview_FY(g, emfy)(i, j, k) : ((n == 0) ? yf(i, j, k) : TF(mfy, i, j));
             double v = 0.5 * (fo + TF(fy2, i, j)) * m;
             if (n == 0 && dfy && dcoef[k] > 1.E-4) v = v + cview_U(g, dfy)(i, j, k);

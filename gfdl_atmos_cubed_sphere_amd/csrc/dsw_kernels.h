@@ -366,11 +366,11 @@ struct DswMomentum {
         if (i <= il + 1 && j <= jl + 1) {
           const double vb = dt5 * (vc[g.iU(i - 1, j)] + vc[g.iU(i, j)]);                       // :1129
           const double ub = ppm_face_sw(&sv(i, j), sv.pitch, vb, g.rdy[g.iV(i, j - 1)], g.rdy[g.iV(i, j)],
-                                        a.hord_mt);                                             // ytp_v :1134
+                                        a.hord_mt, g.lim_fac);                                             // ytp_v :1134
           kev = vb * ub;                                                                        // :1139
           const double ub2 = dt5 * (uc[g.iV(i, j - 1)] + uc[g.iV(i, j)]);                      // :1186
           const double vb2 = ppm_face_sw(&su(i, j), 1, ub2, g.rdx[g.iU(i - 1, j)], g.rdx[g.iU(i, j)],
-                                         a.hord_mt);                                            // xtp_u :1191
+                                         a.hord_mt, g.lim_fac);                                            // xtp_u :1191
           kev = 0.5 * (kev + ub2 * vb2);                                                        // :1196
         }
         ske(i, j) = kev;

@@ -184,8 +184,9 @@ struct DswKeMarch {
     const double d2_bg = a.lv.d2_divg[k];
     const double damp2 = g.da_min_c * dmax(d2_bg, dmin(0.20, a.dddmp * 0.));            // :1454 with vort = 0
     const double dd8 = g.stretched_grid ? g.da_min * ipow(a.d4_bg, 2) : ipow(g.da_min_c * a.d4_bg, 2);  // :1446-1450
-    PpmYsw<SWC> yv;
+    std::conditional_t<(SWC <= 4), PpmYswLin<SWC>, PpmYsw<SWC>> yv;   // 1 .. 4: the linear schemes
     yv.init();
+    if constexpr (SWC <= 4) yv.lim = g.lim_fac;
     for (int r = jA - 3; r <= jB + 2; r++) {
       yv.push(vload(v, (long)g.iV(ilo, r), s.A));
       const int jc = r - 2;
@@ -198,7 +199,11 @@ struct DswKeMarch {
       const vd kev = vb * ub;
       // ---- xtp_u: u advected by ub along x (:1186-1196) ------------------------------------------------------
       const vd ub2 = dt5 * (vload(uc, oVm, s.A) + vload(uc, oV, s.A));
-      const vd vb2 = ppm_faces_x_sw<SWC>(vload(u, oU, s.A), ub2, vload(g.rdx, oU, s.A));
+      vd vb2;
+      if constexpr (SWC <= 4)
+        vb2 = ppm_faces_x_sw_lin<SWC>(vload(u, oU, s.A), ub2, vload(g.rdx, oU, s.A), g.lim_fac);
+      else
+        vb2 = ppm_faces_x_sw<SWC>(vload(u, oU, s.A), ub2, vload(g.rdx, oU, s.A));
       vd kex = 0.5 * (kev + ub2 * vb2);
       // ---- divergence damping, nord = 1 (:1372-1460) -------------------------------------------------------------
       const long oB = (long)g.iB(ilo, jc);

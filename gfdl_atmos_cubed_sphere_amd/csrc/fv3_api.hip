@@ -1379,9 +1379,16 @@ extern "C" int fv3_fv_tp_2d(fv3_ctx *c, int nk, const double *q, const double *c
                             const double *ra_y, const double *mfx, const double *mfy, const double *mass, int nord,
                             double damp_c) {
   if (!c || !c->grid_ready) return fail("fv3_fv_tp_2d: context has no grid (call fv3_grid_upload)");
-  if (!tp_ord_supported_tr(hord)) return fail("fv3_fv_tp_2d: hord=%d not supported (5,-5,6,7,8,9,10,11,12,13)", hord);
+  if (!tp_ord_supported(hord)) return fail("fv3_fv_tp_2d: hord=%d not supported -- " FV3_HORD_TABLE, hord);
   if (nord > 2) return fail("fv3_fv_tp_2d: nord=%d > 2", nord);
   if ((mfx == nullptr) != (mfy == nullptr)) return fail("fv3_fv_tp_2d: mfx and mfy must be given together");
+  // fx, fy are written by tiles / wavefronts whose neighbours still read q and the Courant numbers around the same faces
+  {
+    const double *ins[] = {q, crx, cry, xfx, yfx, ra_x, ra_y, mfx, mfy, mass};
+    bool alias = fx == fy;
+    for (const double *in : ins) alias = alias || (in && (in == fx || in == fy));
+    if (alias) return fail("fv3_fv_tp_2d (nk=%d, hord=%d, nord=%d): fx / fy must not alias an input or each other", nk, hord, nord);
+  }
   if (is_cubed(c)) {
     if (nk > c->g.npz + 1) return fail("fv3_fv_tp_2d: nk > npz + 1 on a cubed-sphere context");
     if (tp2d_cubed(c, nk, q, crx, cry, hord, fx, fy, xfx, yfx, ra_x, ra_y, mfx, mfy)) return 1;
@@ -1435,7 +1442,7 @@ extern "C" int fv3_ppm_line(fv3_ctx *c, int iord, int which, const double *h, co
   if (!c || !c->grid_ready) return fail("fv3_ppm_line: context has no grid");
   if (!h || !cr || !flux || n < 1) return fail("fv3_ppm_line: bad arguments");
   if (which == 0) {
-    if (!tp_ord_supported_tr(iord)) return fail("fv3_ppm_line: iord=%d not supported", iord);
+    if (!tp_ord_supported(iord)) return fail("fv3_ppm_line: hord=%d not supported -- " FV3_HORD_TABLE, iord);
     PpmLineTile kf{h, cr, flux, n, iord, c->g.lim_fac};
     RT(launch_p(c, "ppm_line", Dim3{1, 1, 1}, 1, kf));
     return 0;
@@ -1448,7 +1455,21 @@ extern "C" int fv3_ppm_line(fv3_ctx *c, int iord, int which, const double *h, co
     case 6: RT(launch_w(c, "ppm_line", 1, PpmLineMarch<6>{h, cr, flux, n, which - 1})); break;
     case 8: RT(launch_w(c, "ppm_line", 1, PpmLineMarch<8>{h, cr, flux, n, which - 1})); break;
     case 10: RT(launch_w(c, "ppm_line", 1, PpmLineMarch<10>{h, cr, flux, n, which - 1})); break;
-    default: return fail("fv3_ppm_line: the marching operators are built for iord 5, -5, 6, 8, 10 (what d_sw and update_dz_d take)");
+    case -6: RT(launch_w(c, "ppm_line", 1, PpmLineMarch<-6>{h, cr, flux, n, which - 1})); break;
+    case 7: RT(launch_w(c, "ppm_line", 1, PpmLineMarch<7>{h, cr, flux, n, which - 1})); break;
+    case 9:
+    case 13: RT(launch_w(c, "ppm_line", 1, PpmLineMarch<9>{h, cr, flux, n, which - 1})); break;
+    case 11: RT(launch_w(c, "ppm_line", 1, PpmLineMarch<11>{h, cr, flux, n, which - 1})); break;
+    case 12: RT(launch_w(c, "ppm_line", 1, PpmLineMarch<12>{h, cr, flux, n, which - 1})); break;
+    case 1: RT(launch_w(c, "ppm_line", 1, PpmLineMarchLin<1>{h, cr, flux, n, which - 1, c->g.lim_fac})); break;
+    case -1: RT(launch_w(c, "ppm_line", 1, PpmLineMarchLin<-1>{h, cr, flux, n, which - 1, c->g.lim_fac})); break;
+    case 2: RT(launch_w(c, "ppm_line", 1, PpmLineMarchLin<2>{h, cr, flux, n, which - 1, c->g.lim_fac})); break;
+    case -2: RT(launch_w(c, "ppm_line", 1, PpmLineMarchLin<-2>{h, cr, flux, n, which - 1, c->g.lim_fac})); break;
+    case 3: RT(launch_w(c, "ppm_line", 1, PpmLineMarchLin<3>{h, cr, flux, n, which - 1, c->g.lim_fac})); break;
+    case -3: RT(launch_w(c, "ppm_line", 1, PpmLineMarchLin<-3>{h, cr, flux, n, which - 1, c->g.lim_fac})); break;
+    case 4: RT(launch_w(c, "ppm_line", 1, PpmLineMarchLin<4>{h, cr, flux, n, which - 1, c->g.lim_fac})); break;
+    case -4: RT(launch_w(c, "ppm_line", 1, PpmLineMarchLin<-4>{h, cr, flux, n, which - 1, c->g.lim_fac})); break;
+    default: return fail("fv3_ppm_line: hord=%d not supported -- " FV3_HORD_TABLE, iord);
   }
   return 0;
 }
@@ -1559,6 +1580,24 @@ static int dispatch_hord_tr(int hord, Fn &&fn) {
   return dispatch_hord(hord, fn);
 }
 
+// the whole table, for the per-field marching kernels (DswDelpMarch, DswScalarMarch, DswVortMarch, ZhMarch, TracerMarch): the linear
+// schemes +-1 .. +-4 (PpmYLin) and -6 besides what the fused kernels are built for
+template <class Fn>
+static int dispatch_hord_all(int hord, Fn &&fn) {
+  switch (hord) {
+    case 1: return fn(std::integral_constant<int, 1>());
+    case -1: return fn(std::integral_constant<int, -1>());
+    case 2: return fn(std::integral_constant<int, 2>());
+    case -2: return fn(std::integral_constant<int, -2>());
+    case 3: return fn(std::integral_constant<int, 3>());
+    case -3: return fn(std::integral_constant<int, -3>());
+    case 4: return fn(std::integral_constant<int, 4>());
+    case -4: return fn(std::integral_constant<int, -4>());
+    case -6: return fn(std::integral_constant<int, -6>());
+  }
+  return dispatch_hord_tr(hord, fn);
+}
+
 static int ensure_mflux(fv3_ctx *c) {
   const Grid &g = c->g;
   if (!c->mflux[0]) RT(rt_malloc((void **)&c->mflux[0], sizeof(double) * g.nFX() * g.npz));
@@ -1578,13 +1617,21 @@ static bool dsw_has_interior(const fv3_ctx *c) {
   return mf.nstrips >= 3 && mf.nsegs >= 3 && last_cols >= 3 && last_rows >= 3;
 }
 
+// (the fused kernel is instantiated for tp_ord_fused; any other order of the table runs on the per-field kernels)
+static bool dsw_transport_fused(const fv3_ctx *c, const DswArgs &a) {
+  return c->use_fused && !a.use_cond && a.hord_dp == a.hord_tm && (a.hydrostatic || a.hord_dp == a.hord_vt) && tp_ord_fused(a.hord_dp);
+}
+// (DswMomentumFused<wind class, hord_vt>)
+static bool dsw_momentum_fused(const fv3_ctx *c, const DswArgs &a) {
+  return c->use_fused != 0 && tp_ord_fused(a.hord_vt) && sw_ord_fused(a.hord_mt);
+}
 static int dsw_transport_march(fv3_ctx *c, const DswArgs &a, int region = 0) {
   const Grid &g = c->g;
   if (ensure_mflux(c)) return 1;
   MarchDims md = make_march_dims(g, seg_rows(c, c->march_tj, g.npz));
   md.klist = c->klist;
   const int nw = md.nwaves(c->n_plain);
-  if (c->use_fused && !a.use_cond && a.hord_dp == a.hord_tm && (a.hydrostatic || a.hord_dp == a.hord_vt)) {
+  if (dsw_transport_fused(c, a)) {
     if (c->n_plain == 0) return 0;
     // (the interior of a cubed-sphere face, six faces a launch: seven 55-row segments measured 3 % better than eight of 48 there)
     MarchDims mf = make_march_dims(g, seg_rows(c, (a.mask_w && !c->tj_env_fused) ? 55 : c->march_tj_fused, g.npz));
@@ -1624,13 +1671,13 @@ static int dsw_transport_march(fv3_ctx *c, const DswArgs &a, int region = 0) {
   }
   if (region == 1) return 0;  // the per-field kernels are not split
   double *fxs = c->mflux[0], *fys = c->mflux[1];
-  int rc = dispatch_hord(a.hord_dp, [&](auto H) {
+  int rc = dispatch_hord_all(a.hord_dp, [&](auto H) {
     DswDelpMarch<decltype(H)::value> kf{g, a, md, fxs, fys, 1};
     return launch_w(c, "d_sw_delp", nw, kf);
   });
   if (rc) return rc;
   auto scalar = [&](const char *label, int hord, const double *q, double *q_out) {
-    return dispatch_hord(hord, [&](auto H) {
+    return dispatch_hord_all(hord, [&](auto H) {
       DswScalarMarch<decltype(H)::value> kf{g, a, md, fxs, fys, q, q_out};
       return launch_w(c, label, nw, kf);
     });
@@ -1644,7 +1691,7 @@ static int dsw_transport_march(fv3_ctx *c, const DswArgs &a, int region = 0) {
 // part = 0: everything; 1: only the KE / damping kernel (unfused path); 2: only the vorticity kernel
 static int dsw_momentum_march(fv3_ctx *c, const DswArgs &a, int part = 0) {
   const Grid &g = c->g;
-  const bool fused_m = c->use_fused != 0;
+  const bool fused_m = dsw_momentum_fused(c, a);
   if (!fused_m && !c->ke_scr) RT(rt_malloc((void **)&c->ke_scr, sizeof(double) * g.nB() * g.npz));
   if (fused_m) {
     MarchDims mf = make_march_dims(g, seg_rows(c, (a.mask_w && !c->tj_env_fused) ? 55 : c->march_tj_mom, g.npz));
@@ -1685,6 +1732,10 @@ static int dsw_momentum_march(fv3_ctx *c, const DswArgs &a, int part = 0) {
     const int nwk = mk.nwaves(c->n_plain_m);
     int rc;
     switch (sw_class(a.hord_mt)) {
+      case 1: rc = launch_w(c, "d_sw_ke", nwk, DswKeMarch<1>{g, a, mk, c->ke_scr}); break;
+      case 2: rc = launch_w(c, "d_sw_ke", nwk, DswKeMarch<2>{g, a, mk, c->ke_scr}); break;
+      case 3: rc = launch_w(c, "d_sw_ke", nwk, DswKeMarch<3>{g, a, mk, c->ke_scr}); break;
+      case 4: rc = launch_w(c, "d_sw_ke", nwk, DswKeMarch<4>{g, a, mk, c->ke_scr}); break;
       case 5: rc = launch_w(c, "d_sw_ke", nwk, DswKeMarch<5>{g, a, mk, c->ke_scr}); break;
       case 6: rc = launch_w(c, "d_sw_ke", nwk, DswKeMarch<6>{g, a, mk, c->ke_scr}); break;
       default: rc = launch_w(c, "d_sw_ke", nwk, DswKeMarch<8>{g, a, mk, c->ke_scr}); break;
@@ -1695,7 +1746,7 @@ static int dsw_momentum_march(fv3_ctx *c, const DswArgs &a, int part = 0) {
   md.klist = c->klist_m;
   const int nw = md.nwaves(c->n_plain_m);
   const double *ke = c->ke_scr;
-  return dispatch_hord(a.hord_vt, [&](auto H) {
+  return dispatch_hord_all(a.hord_vt, [&](auto H) {
     DswVortMarch<decltype(H)::value> kf{g, a, md, ke};
     return launch_w(c, "d_sw_vort", nw, kf);
   });
@@ -1789,7 +1840,10 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
   // formed on a frame wider by the reach of the pass chain.  Levels the marching kernels do not take (sponge-level damping,
   // nord_k /= 1) go through the passes on the whole face.
   const int wo = c->cubed_frame, wm = wo + c->cubed_reach;
-  const bool fits = wo > 0 && npx - 1 >= 2 * wm + 8 && npx == npy;
+  // (the interior of the hybrid is the fused kernels': an order they are not instantiated for -- tp_ord_fused, sw_ord_fused -- sends
+  // the whole face through the pass kernels, the path small faces take)
+  const bool fused_ord = tp_ord_fused(a.hord_dp) && tp_ord_fused(a.hord_vt) && tp_ord_fused(a.hord_tm) && sw_ord_fused(a.hord_mt);
+  const bool fits = wo > 0 && npx - 1 >= 2 * wm + 8 && npx == npy && fused_ord;
   const bool fused_ok = c->use_march && c->use_fused && !a.use_cond && a.hord_dp == a.hord_tm && (a.hydrostatic || a.hord_dp == a.hord_vt);
   const bool hyb_t = fits && fused_ok && c->n_plain > 0;
   const bool hyb_m = fits && c->use_march && c->use_fused && c->n_plain_m > 0 && a.dddmp < 1.E-5 && !g.do_diss_est;
@@ -2095,9 +2149,9 @@ static int d_sw_impl(fv3_ctx *c, const fv3_dsw_params *p, double *delpc, const d
   if (!c || !c->grid_ready) return fail("fv3_d_sw: context has no grid (call fv3_grid_upload)");
   if (!c->lev_ready) return fail("fv3_d_sw: per-level coefficients missing (call fv3_dsw_levels_upload)");
   if (!p) return fail("fv3_d_sw: null params");
-  if (!tp_ord_supported(p->hord_dp) || !tp_ord_supported(p->hord_vt) || !tp_ord_supported(p->hord_tm))
-    return fail("fv3_d_sw: hord_dp/vt/tm must be one of 5,-5,6,8,10");
-  if (!sw_ord_supported(p->hord_mt)) return fail("fv3_d_sw: hord_mt must be in 5..11");
+  for (int h : {p->hord_dp, p->hord_vt, p->hord_tm})
+    if (!tp_ord_supported(h)) return fail("fv3_d_sw: hord=%d not supported -- " FV3_HORD_TABLE, h);
+  if (!sw_ord_supported(p->hord_mt)) return fail("fv3_d_sw: hord=%d not supported -- " FV3_HORD_TABLE, p->hord_mt);
   if (!p->hydrostatic && (!w || !w_out)) return fail("fv3_d_sw: nonhydrostatic call needs w and w_out");
   if (p->use_cond && (!q_con || !q_con_out)) return fail("fv3_d_sw: use_cond needs q_con and q_con_out");
   if (delp == delp_out || pt == pt_out || u == u_out || v == v_out || (w && w == w_out))
@@ -2132,18 +2186,20 @@ static int d_sw_impl(fv3_ctx *c, const fv3_dsw_params *p, double *delpc, const d
     return dsw_cubed(c, a);
   }
   // the fused marching kernel forms the Courant numbers itself for its levels
-  const bool fused = c->use_march && c->use_fused && !a.use_cond && a.hord_dp == a.hord_tm &&
-                     (a.hydrostatic || a.hord_dp == a.hord_vt);
+  const bool fused = c->use_march && dsw_transport_fused(c, a);
+  // ... and so is the momentum half (what every build of the fused transport kernel had beside it before the order table grew: the
+  // branch-free forms, the sponge levels on the marching kernels and the side stream below assume both)
+  const bool fused_m = dsw_momentum_fused(c, a);
   constexpr int TI = FV3_DSW_TI, TJ = FV3_DSW_TJ;
   const bool march = c->use_march != 0;
   // marching momentum: no Smagorinsky coefficient, no dissipation estimate (level conditions in klist_m)
   const bool march_m = march && a.dddmp < 1.E-5 && !g.do_diss_est;
   // the sponge levels on the marching kernels: their branch-free forms with uniform metrics, both halves of d_sw marching
-  lev_activate(c, (FV3_BF && c->sponge_march && g.geom == 2 && fused && march_m) ? 1 : 0);
+  lev_activate(c, (FV3_BF && c->sponge_march && g.geom == 2 && fused && fused_m && march_m) ? 1 : 0);
   // heat_s, diss_e = NULL: the caller does not read them (dyn_core.F90:798-812 reads them when d_con > 1e-5 or do_diss_est; in the
   // reference they are 2-D work arrays private to a level).  The branch-free marching kernels then do not store them; every other kernel
   // writes (and the damped levels' momentum kernels read) real arrays, the context's own
-  const bool all_bf = FV3_BF && fused && march_m && c->n_damp == 0 && c->n_rest_m == 0;
+  const bool all_bf = FV3_BF && fused && fused_m && march_m && c->n_damp == 0 && c->n_rest_m == 0;
   if ((!a.heat_s || !a.diss_e) && !all_bf) {
     for (int n = 0; n < 2; n++)
       if (!c->heat_scr[n]) RT(rt_malloc((void **)&c->heat_scr[n], sizeof(double) * g.nCC() * npz));
@@ -2188,7 +2244,7 @@ static int d_sw_impl(fv3_ctx *c, const fv3_dsw_params *p, double *delpc, const d
     return 0;
   }
   const int region = (phase == 2 && split) ? 2 : 0;
-  const bool side = fused && march_m && c->side_ok && c->use_side && !c->prof_on && !c->grp && c->n_damp > 0 && c->n_plain > 0;
+  const bool side = fused && fused_m && march_m && c->side_ok && c->use_side && !c->prof_on && !c->grp && c->n_damp > 0 && c->n_plain > 0;
   if (side) {
     if (!c->stream2) {
       RT(rt_stream_create(&c->stream2));
@@ -3389,7 +3445,7 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, int hord, const double *zs, const dou
   if (!c || !c->grid_ready) return fail("fv3_update_dz_d: context has no grid");
   if (!c->dp0_ready) return fail("fv3_update_dz_d: call fv3_set_dp_ref first");
   if (!c->lev_ready) return fail("fv3_update_dz_d: call fv3_dsw_levels_upload first");
-  if (!tp_ord_supported(hord)) return fail("fv3_update_dz_d: hord=%d not supported", hord);
+  if (!tp_ord_supported(hord)) return fail("fv3_update_dz_d: hord=%d not supported -- " FV3_HORD_TABLE, hord);
   if (zh_in == zh_out) return fail("fv3_update_dz_d: zh_in and zh_out must not alias");
   if (need_scratch(c, 4)) return 1;  // crx_adv, xfx_adv (CX x (km+1)), cry_adv, yfx_adv (CY x (km+1)) fit in A x (km+1)
   const Grid &g = c->g;
@@ -3414,7 +3470,7 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, int hord, const double *zs, const dou
       MarchDims md = make_march_dims(g, seg_rows(c, c->march_tj, g.npz));
       md.klist = c->klist_z;
       const int nwz = md.nwaves(c->n_plain_z);
-      RT(dispatch_hord(hord, [&](auto H) {
+      RT(dispatch_hord_all(hord, [&](auto H) {
         ZhMarch<decltype(H)::value> kf{g, md, zh_in, cxa, cya, xfa, yfa, zh_out};
         return launch_w(c, "zh_transport", nwz, kf);
       }));
@@ -3464,7 +3520,7 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, int hord, const double *zs, const dou
     MarchDims md = make_march_dims(g, seg_rows(c, c->march_tj, g.npz));
     md.klist = c->klist_z;
     const int nwz = md.nwaves(c->n_plain_z);
-    RT(dispatch_hord(hord, [&](auto H) {
+    RT(dispatch_hord_all(hord, [&](auto H) {
       ZhMarch<decltype(H)::value> kf{g, md, zh_in, cxa, cya, xfa, yfa, zh_out};
       return launch_w(c, "zh_transport", nwz, kf);
     }));
@@ -4269,7 +4325,7 @@ extern "C" int fv3_tracer_2d_step(fv3_ctx *c, int it, int nsplt, const int *kspl
                                   const double *mfx, const double *mfy, const double *cx, const double *cy,
                                   const double *xfx, const double *yfx) {
   if (!c || !c->grid_ready || !ksplt_host) return fail("fv3_tracer_2d_step: bad context/arguments");
-  if (!tp_ord_supported_tr(hord)) return fail("fv3_tracer_2d_step: hord=%d not supported (5,-5,6,7,8,9,10,11,12,13)", hord);
+  if (!tp_ord_supported(hord)) return fail("fv3_tracer_2d_step: hord=%d not supported -- " FV3_HORD_TABLE, hord);
   if (q == q_out || dp1 == dp1_out) return fail("fv3_tracer_2d_step: *_out buffers must not alias the inputs");
   if (trdm > 1.e-4 && nord_tr > 2) return fail("fv3_tracer_2d_step: nord_tr > 2");
   if (need_trc(c)) return 1;
@@ -4290,7 +4346,7 @@ extern "C" int fv3_d_sw_inline_q(fv3_ctx *c, int nq, int hord_tr, int nord_t, do
   if (!c || !c->grid_ready) return fail("fv3_d_sw_inline_q: context has no grid");
   if (nq < 1 || !q || !q_out || !delp_old || !delp_new || !fx || !fy || !crx || !cry || !xfx || !yfx)
     return fail("fv3_d_sw_inline_q: null argument");
-  if (!tp_ord_supported_tr(hord_tr)) return fail("fv3_d_sw_inline_q: hord_tr=%d not supported (5,-5,6,7,8,9,10,11,12,13)", hord_tr);
+  if (!tp_ord_supported(hord_tr)) return fail("fv3_d_sw_inline_q: hord=%d not supported -- " FV3_HORD_TABLE, hord_tr);
   if (q == q_out) return fail("fv3_d_sw_inline_q: q_out must not alias q");
   if (damp_t > 1.e-4 && nord_t > 2) return fail("fv3_d_sw_inline_q: nord_t > 2");
   if (need_trc(c)) return 1;
@@ -4358,7 +4414,7 @@ static int tracer_step_impl(fv3_ctx *c, int it, int nsplt, const int *ksplt_dev,
   const Grid &g = c->g;
   auto march_step = [&]() -> int {
     const int trc_nt = c->trc_nt;   // tracers per wavefront (1: one (tracer, level) per wavefront, TracerMarch)
-    if (trc_nt > 1 && nq > 1) {
+    if (trc_nt > 1 && nq > 1 && tp_ord_fused_tr(hord)) {   // (the other orders: one (tracer, level) per wavefront)
       auto go = [&](auto H, auto NTc) -> int {
         constexpr int NT = decltype(NTc)::value;
         const int ngrp = (nq + NT - 1) / NT;
@@ -4377,7 +4433,7 @@ static int tracer_step_impl(fv3_ctx *c, int it, int nsplt, const int *ksplt_dev,
     }
     MarchDims md = make_march_dims(g, seg_rows(c, c->march_tj, g.npz));
     const int nwt = md.nwaves(g.npz * nq);
-    return dispatch_hord_tr(hord, [&](auto H) {
+    return dispatch_hord_all(hord, [&](auto H) {
       TracerMarch<decltype(H)::value> kf{g, md, g.npz, nq, it, nsplt, ksplt_dev, q, dp1, mfx, mfy, cx, cy, xfx, yfx,
                                          q_out, dp1_out};
       return launch_w(c, "tracer_step", nwt, kf);

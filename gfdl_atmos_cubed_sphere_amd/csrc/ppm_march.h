@@ -90,7 +90,7 @@ FV3_D PCell ppm_cell_mono(const vd &qm2, const vd &qm1, const vd &q0, const vd &
   return c;
 }
 
-// ORD in {5, -5, 6}: al0 = al(i), al1 = al(i+1)  (tp_core.F90:371-397, :499-524)
+// ORD in {5, -5, 6, -6}: al0 = al(i), al1 = al(i+1)  (tp_core.F90:371-397, :499-524); -6 is 6 on the clamped al
 template <int ORD>
 FV3_D PCell ppm_cell_unlim(const vd &q0, const vd &al0, const vd &al1) {
   constexpr double r12 = 1. / 12.;
@@ -98,7 +98,7 @@ FV3_D PCell ppm_cell_unlim(const vd &q0, const vd &al0, const vd &al1) {
   c.q = q0;
   vd bl = al0 - q0, br = al1 - q0;
   const vd b0 = bl + br;
-  if (ORD == 6)
+  if (ORD == 6 || ORD == -6)
     c.smt = 3. * vabs(b0) < vabs(bl - br);
   else
     c.smt = bl * br < 0.;
@@ -297,7 +297,8 @@ struct PpmY {
 
 // =====================================================================================================
 // sw_core flavour (xtp_u / ytp_v).  SWC = scheme class: 5 (iord 5), 6 (iord 6, 7), 8 (iord >= 8).
-constexpr int sw_class(int iord) { return iord >= 8 ? 8 : (iord == 5 ? 5 : 6); }
+// (1 .. 4: the linear schemes, classes of their own -- PpmYswLin below)
+constexpr int sw_class(int iord) { return iord >= 8 ? 8 : (iord <= 5 ? iord : 6); }
 // the classes of the cubed-sphere branch away from the face edges (iord = 9 is the "other grids" form)
 constexpr int sw_class_cubed(int iord) { return iord == 8 ? 108 : (iord == 10 ? 110 : (iord == 11 ? 111 : sw_class(iord))); }
 
@@ -366,6 +367,176 @@ struct PpmYsw {
 };
 
 // =====================================================================================================
+// The linear schemes |ORD| = 1 .. 4 of xppm / yppm (tp_core.F90:394-487) and 1 .. 4 of xtp_u / ytp_v (sw_core.F90:2245-2335).
+// They need more per cell than PCell holds -- hord 3 / 4 a second flag, hord 2 the sum of the cell's two al in the reference's
+// association -- so they have a cell type, an x operator and a register window of their own; the kernels of the other families
+// carry none of it.  lim = flagstruct%lim_fac (Grid::lim_fac), read by hord 1 alone.
+constexpr bool ppm_is_lin(int ord) { return ord >= -4 && ord <= 4 && ord != 0; }
+
+struct PCellL {
+  vd q, bl, br, b0;
+  vb s5, s6;   // hord 1: s5 = abs(lim_fac * b0) < abs(bl - br); hord 3, 4: s5 = x0 < xt, s6 = 3 * x0 < xt
+};
+
+FV3_D vb vb_shr1(const vb &f) {  // the flag of the lane to the left (lane 0: false)
+#ifdef FV3_HOST_EMU
+  vb m;
+  m.v[0] = false;
+  for (int l = 1; l < kW; l++) m.v[l] = f.v[l - 1];
+  return m;
+#else
+  return __builtin_amdgcn_update_dpp(0, (int)f, 0x138, 0xf, 0xf, true) != 0;
+#endif
+}
+
+// WIND = false: tp_core.F90 (hord 2 is written on al: al(i-1) + al(i) - (q + q), :413-429); true: sw_core.F90 (bl + br throughout)
+template <int ORD, bool WIND = false>
+FV3_D PCellL ppm_cell_lin(const vd &q0, const vd &al0, const vd &al1, double lim) {
+  constexpr int M = ORD < 0 ? -ORD : ORD;
+  PCellL c;
+  c.q = q0;
+  c.bl = al0 - q0;
+  c.br = al1 - q0;
+  c.s5 = c.s6 = vball(false);
+  if (M == 2 && !WIND) {
+    c.b0 = al0 + al1 - (q0 + q0);
+    return c;
+  }
+  c.b0 = c.bl + c.br;
+  const vd x0 = vabs(c.b0), xt = vabs(c.bl - c.br);
+  if (M == 1) {
+    c.s5 = vabs(lim * c.b0) < xt;
+  } else if (M != 2) {
+    c.s5 = x0 < xt;
+    c.s6 = 3. * x0 < xt;
+  }
+  return c;
+}
+
+FV3_D PCellL shift_cell_lin_r(const PCellL &c) {
+  PCellL m;
+  m.q = shr1(c.q);
+  m.bl = shr1(c.bl);
+  m.br = shr1(c.br);
+  m.b0 = shr1(c.b0);
+  m.s5 = vb_shr1(c.s5);
+  m.s6 = vb_shr1(c.s6);
+  return m;
+}
+
+// face between cell m and cell p, Courant number c: (1 + c) == 1 - |c| and bl + c * b0 == bl - |c| * b0 bit for bit when c <= 0
+template <int ORD>
+FV3_D vd ppm_face_lin(const PCellL &m, const PCellL &p, const vd &c) {
+  constexpr int M = ORD < 0 ? -ORD : ORD;
+  const vb pos = c > 0.;
+  const vd s = vabs(c);
+  const vd qu = vsel(pos, m.q, p.q);
+  const vd x = vsel(pos, m.br, p.bl);
+  const vd b0 = vsel(pos, m.b0, p.b0);
+  const vd f = qu + (1. - s) * (x - s * b0);
+  if (M == 2) return f;                                                    // :413-429
+  vb on;
+  if (M == 1)
+    on = m.s5 || p.s5;                                                     // :394-411
+  else if (M == 3)
+    on = vselb(pos, m.s5 || p.s6, m.s6 || p.s5);                           // :431-457: asymmetric about the face
+  else
+    on = (m.s5 && p.s5) || m.s6 || p.s6;                                   // :459-487
+  return vsel(on, f, qu);
+}
+
+// x: face l between lanes l-1 and l; valid faces: lanes 3..61 (the stencil of the unlimited family)
+template <int ORD>
+FV3_D vd ppm_faces_x_lin(const vd &q, const vd &c, double lim) {
+  const vd qm1 = shr1(q), qp1 = shl1(q);
+  const vd al0 = ppm_al_unlim<ORD>(shr1(qm1), qm1, q, qp1);
+  const PCellL p = ppm_cell_lin<ORD>(q, al0, shl1(al0), lim);
+  return ppm_face_lin<ORD>(shift_cell_lin_r(p), p, c);
+}
+
+// y: the register window, the interface of PpmY
+template <int ORD>
+struct PpmYLin {
+  vd q1, q2, q3, q4;  // rows r-3 .. r
+  vd al2, al3;
+  PCellL prev, cur;
+  double lim;
+  FV3_D void init() {
+    q1 = q2 = q3 = q4 = vd(0.);
+    al2 = al3 = vd(0.);
+    prev.q = prev.bl = prev.br = prev.b0 = vd(0.);
+    prev.s5 = prev.s6 = vball(false);
+    cur = prev;
+    lim = 1.;
+  }
+  FV3_D void push(const vd &qn) {
+    q1 = q2; q2 = q3; q3 = q4; q4 = qn;
+    prev = cur;
+    al2 = al3;
+    al3 = ppm_al_unlim<ORD>(q1, q2, q3, q4);    // edge (r-2 | r-1)
+    cur = ppm_cell_lin<ORD>(q2, al2, al3, lim);
+  }
+  FV3_D vd face(const vd &c) const { return ppm_face_lin<ORD>(prev, cur, c); }
+  FV3_D const vd &row_m3() const { return q1; }
+};
+template <> struct PpmY<1> : PpmYLin<1> {};
+template <> struct PpmY<-1> : PpmYLin<-1> {};
+template <> struct PpmY<2> : PpmYLin<2> {};
+template <> struct PpmY<-2> : PpmYLin<-2> {};
+template <> struct PpmY<3> : PpmYLin<3> {};
+template <> struct PpmY<-3> : PpmYLin<-3> {};
+template <> struct PpmY<4> : PpmYLin<4> {};
+template <> struct PpmY<-4> : PpmYLin<-4> {};
+
+// ---- the wind operator, SWC = iord = 1 .. 4 -----------------------------------------------------------
+template <int SWC>
+FV3_D vd ppm_face_sw_lin(const PCellL &m, const PCellL &p, const vd &c, const vd &rdm, const vd &rdp) {
+  const vb pos = c > 0.;
+  const vd s = vabs(vsel(pos, c * rdm, c * rdp));
+  const vd wu = vsel(pos, m.q, p.q);
+  const vd x = vsel(pos, m.br, p.bl);
+  const vd par = x - s * vsel(pos, m.b0, p.b0);   // the parabolic flux without its (1 -+ cfl)
+  const vd fac = 1. - s;
+  if (SWC == 2) return wu + fac * par;                                     // :2264-2275
+  if (SWC == 1) return vsel(m.s5 || p.s5, wu + fac * par, wu);             // :2245-2262
+  const vb hi5 = m.s5 && p.s5, hi6 = m.s6 || p.s6;
+  if (SWC == 4) return vsel(hi5 || hi6, wu + fac * par, wu);               // :2310-2335
+  // :2277-2308 -- not the scalar operator's 3: hi6 the parabola, else hi5 the smaller of bl, br with the sign of the near one
+  const vd mono = vsign(vmin(vabs(vsel(pos, m.bl, p.bl)), vabs(vsel(pos, m.br, p.br))), x);
+  return wu + fac * vsel(hi6, par, vsel(hi5, mono, vd(0.)));
+}
+template <int SWC>
+FV3_D vd ppm_faces_x_sw_lin(const vd &q, const vd &c, const vd &rd, double lim) {
+  const vd qm1 = shr1(q), qp1 = shl1(q);
+  const vd al0 = ppm_al_unlim<5>(shr1(qm1), qm1, q, qp1);
+  const PCellL p = ppm_cell_lin<SWC, true>(q, al0, shl1(al0), lim);
+  return ppm_face_sw_lin<SWC>(shift_cell_lin_r(p), p, c, shr1(rd), rd);
+}
+template <int SWC>
+struct PpmYswLin {
+  vd q1, q2, q3, q4;
+  vd al2, al3;
+  PCellL prev, cur;
+  double lim;
+  FV3_D void init() {
+    q1 = q2 = q3 = q4 = vd(0.);
+    al2 = al3 = vd(0.);
+    prev.q = prev.bl = prev.br = prev.b0 = vd(0.);
+    prev.s5 = prev.s6 = vball(false);
+    cur = prev;
+    lim = 1.;
+  }
+  FV3_D void push(const vd &qn) {
+    q1 = q2; q2 = q3; q3 = q4; q4 = qn;
+    prev = cur;
+    al2 = al3;
+    al3 = ppm_al_unlim<5>(q1, q2, q3, q4);
+    cur = ppm_cell_lin<SWC, true>(q2, al2, al3, lim);
+  }
+  FV3_D vd face(const vd &c, const vd &rdm, const vd &rdp) const { return ppm_face_sw_lin<SWC>(prev, cur, c, rdm, rdp); }
+};
+
+// =====================================================================================================
 // fv3_ppm_line: ONE line through the 1-D operators of the marching kernels -- the unit-test surface for the reference-held vectors of
 // xppm / yppm (tests/golden/ppm1d_golden.npz), iord 10 among them: inside fv_tp_2d the inner sweep of hord 10 is ord 8
 // (tp_core.F90:136-141), so those vectors cannot pass through it unchanged.  h: the line with its 3 halo cells on either side
@@ -391,6 +562,31 @@ struct PpmLineMarch {
       for (int r = 0; r < n + 6; r++) {
         w.push(vload(h, r, l0));
         if (r >= 5) vstore(flux, r - 5, w.face(vload(c, r - 5, l0)), 0, 0);   // face f = r - 4 (1-based) between cells f - 1 and f
+      }
+    }
+  }
+};
+
+// the same for the linear schemes, with lim_fac
+template <int ORD>
+struct PpmLineMarchLin {
+  const double *h, *c;
+  double *flux;
+  int n, along;
+  double lim;
+  FV3_D void operator()(int) const {
+    if (along == 0) {
+      const vl li = make_lanes(0, n + 5), lf = make_lanes(3, n + 3);
+      const vd f = ppm_faces_x_lin<ORD>(vload(h, 0, li), vload(c, -3, lf), lim);
+      vstore(flux, -3, f, 3, n + 3);
+    } else {
+      const vl l0 = make_lanes(0, 0);
+      PpmY<ORD> w;
+      w.init();
+      w.lim = lim;
+      for (int r = 0; r < n + 6; r++) {
+        w.push(vload(h, r, l0));
+        if (r >= 5) vstore(flux, r - 5, w.face(vload(c, r - 5, l0)), 0, 0);
       }
     }
   }

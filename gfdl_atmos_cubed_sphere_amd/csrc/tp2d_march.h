@@ -211,7 +211,10 @@ struct Tp2dState {
     const vd arj = UNI_AREA ? in.ar : ar_3, cxj = cx_3;  // rows r-3 (valid once three rows have been consumed)
     if constexpr (!UNI_AREA) { ar_3 = ar_2; ar_2 = ar_1; ar_1 = in.ar; }
     cx_3 = cx_2; cx_2 = cx_1; cx_1 = in.cx;
-    fx2_0 = ppm_faces_x<ORD_IN>(in.qn, in.cx);
+    if constexpr (ppm_is_lin(ORD_IN))
+      fx2_0 = ppm_faces_x_lin<ORD_IN>(in.qn, in.cx, ya.lim);
+    else
+      fx2_0 = ppm_faces_x<ORD_IN>(in.qn, in.cx);
     const vd t = in.xf * fx2_0;
     const vd rax = in.ar + in.xf - shl1(in.xf);
     const vd qj = vdiv_r(in.qn * in.ar + t - shl1(t), rax, vrecip(rax));  // correctly rounded, 8 instructions instead of 11
@@ -227,7 +230,11 @@ struct Tp2dState {
     if (have_row) {
       const vd ray = arj + yf_prev - in.yf;
       const vd qi = vdiv_r(ya.row_m3() * arj + fy2y_prev - fy2y, ray, vrecip(ray));
-      const vd fxo = ppm_faces_x<ORD_OU>(qi, cxj);
+      vd fxo;
+      if constexpr (ppm_is_lin(ORD_OU))
+        fxo = ppm_faces_x_lin<ORD_OU>(qi, cxj, yb.lim);
+      else
+        fxo = ppm_faces_x<ORD_OU>(qi, cxj);
       fxv = 0.5 * (fxo + fx2_3);
       fyv0 = fyv_prev;
       fyv1 = fyv;
@@ -276,6 +283,7 @@ FV3_D void tp2d_march_src(const Grid &g, const StripGeom &s, int jA, int jB, con
                           const double *cry, const double *xfx, const double *yfx, Sink &sink) {
   Tp2dState<HORD> st;
   st.init();
+  if constexpr (ppm_is_lin(HORD)) st.ya.lim = st.yb.lim = g.lim_fac;   // hord 1 reads it
   const int rlast = jB + 3;
   MarchIn nxt;
   march_load_metrics(nxt, g, s, jA, jA - 3, crx, cry, xfx, yfx);

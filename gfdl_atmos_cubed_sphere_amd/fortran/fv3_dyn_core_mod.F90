@@ -571,7 +571,7 @@ contains
       fl%use_old_omega = flagstruct%use_old_omega; fl%is_ideal_case = flagstruct%is_ideal_case
       fl%n_sponge = flagstruct%n_sponge
       fl%hord_mt = flagstruct%hord_mt;    fl%hord_vt = flagstruct%hord_vt;   fl%hord_tm = flagstruct%hord_tm
-      fl%hord_dp = flagstruct%hord_dp;    fl%hord_tr = flagstruct%hord_tr
+      fl%hord_dp = flagstruct%hord_dp;    fl%hord_tr = flagstruct%hord_tr;   fl%lim_fac = flagstruct%lim_fac
       fl%kord_tm = flagstruct%kord_tm;    fl%kord_mt = flagstruct%kord_mt;   fl%kord_wz = flagstruct%kord_wz
       fl%kord_tr = flagstruct%kord_tr;    fl%nord_tr = flagstruct%nord_tr;   fl%trdm2 = flagstruct%trdm2
       fl%a_imp = flagstruct%a_imp;        fl%p_fac = flagstruct%p_fac;       fl%ptop = ptop
@@ -1027,7 +1027,7 @@ contains
     fl%use_old_omega = flagstruct%use_old_omega; fl%is_ideal_case = flagstruct%is_ideal_case
     fl%n_sponge = flagstruct%n_sponge
     fl%hord_mt = flagstruct%hord_mt;    fl%hord_vt = flagstruct%hord_vt;   fl%hord_tm = flagstruct%hord_tm
-    fl%hord_dp = flagstruct%hord_dp;    fl%hord_tr = flagstruct%hord_tr
+    fl%hord_dp = flagstruct%hord_dp;    fl%hord_tr = flagstruct%hord_tr;   fl%lim_fac = flagstruct%lim_fac
     fl%kord_tm = flagstruct%kord_tm;    fl%kord_mt = flagstruct%kord_mt;   fl%kord_wz = flagstruct%kord_wz
     fl%kord_tr = flagstruct%kord_tr;    fl%nord_tr = flagstruct%nord_tr;   fl%trdm2 = flagstruct%trdm2
     fl%a_imp = flagstruct%a_imp;        fl%p_fac = flagstruct%p_fac;       fl%m_split = max(1, flagstruct%m_split)

@@ -38,6 +38,7 @@ module fv3_host_mod
     logical :: do_vort_damp = .false., use_logp = .false., use_old_omega = .true., is_ideal_case = .false.
     integer :: n_sponge = 1
     integer :: hord_mt = 10, hord_vt = 10, hord_tm = 10, hord_dp = 10, hord_tr = 8
+    real(c_double) :: lim_fac = 1.d0                  ! the factor of the smoothness flag of hord = 1 (tp_core.F90:394-411)
     integer :: kord_tm = -8, kord_mt = 8, kord_wz = 8, kord_tr = 8
     integer :: nord_tr = 0
     real(c_double) :: trdm2 = 0.d0
@@ -223,7 +224,7 @@ contains
 
     dom%is = 1; dom%ie = nx; dom%js = 1; dom%je = ny; dom%ng = NG
     dom%npx = nx + 1; dom%npy = ny + 1; dom%npz = npz; dom%grid_type = 4
-    dom%do_diss_est = 0; dom%prevent_diss_cooling = 1; dom%stretched_grid = 0; dom%lim_fac = 1.d0
+    dom%do_diss_est = 0; dom%prevent_diss_cooling = 1; dom%stretched_grid = 0; dom%lim_fac = fl%lim_fac
 
     ! ---- gridstruct: every metric term is a constant on this domain; one host array per distinct value is enough,
     !      sized for the largest stagger (B) -- fv3_grid_upload copies the leading part it needs

@@ -64,7 +64,7 @@ program fv3_solo_sphere
   fl%remap_te = iand(hydrostatic, 4_c_int) /= 0                                                           ! bit 2: remap_te
   fl%d_con = d_con; fl%d_ext = d_ext; fl%beta = beta
   dom%is = 1; dom%ie = nx; dom%js = 1; dom%je = nx; dom%ng = 3; dom%npx = npx; dom%npy = npx; dom%npz = npz; dom%grid_type = 0
-  dom%do_diss_est = 0; dom%prevent_diss_cooling = 1; dom%stretched_grid = 0; dom%lim_fac = 1.d0
+  dom%do_diss_est = 0; dom%prevent_diss_cooling = 1; dom%stretched_grid = 0; dom%lim_fac = fl%lim_fac
   do t = 1, 6
     gh%da_min = da_min; gh%da_min_c = da_min_c
     gh%area = c_loc(gm(t)%a(isd,isd,1)); gh%rarea = c_loc(gm(t)%a(isd,isd,2)); gh%dxa = c_loc(gm(t)%a(isd,isd,3))

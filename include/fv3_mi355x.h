@@ -50,7 +50,7 @@ typedef struct fv3_domain {
   int npx, npy, npz;  /* global corner counts and number of levels */
   int grid_type;      /* 4 = doubly periodic (Cartesian), 0..2 = a face of the cubed sphere */
   int do_diss_est, prevent_diss_cooling, stretched_grid;
-  double lim_fac;
+  double lim_fac;      /* flagstruct%lim_fac (fv_arrays.F90): the factor of the smoothness flag of hord = 1, read by no other order */
 } fv3_domain;
 
 /* gridstruct members (model/fv_arrays.F90:75-205; shapes :1749-1881).  HOST pointers; copied to
@@ -144,8 +144,11 @@ int fv3_registry_stats(fv3_ctx *ctx, long long *out4);
 /* fv_tp_2d -- model/tp_core.F90:85-87 (called from sw_core.F90:919,983,993,1014,1498,
  * nh_utils.F90:279,289, fv_tracer2d.F90:504,509).  nk slabs.  q: A; crx,xfx: CX; cry,yfx: CY;
  * ra_x: (is:ie, jsd:jed); ra_y: (isd:ied, js:je); fx,mfx: FX; fy,mfy: FY; mass: A.
- * Optional arguments are NULL / nord < 0 when absent.  hord: 5, -5, 6, 7, 8, 9, 10, 11, 12, 13 (xppm / yppm, :365-707;
- * d_sw and update_dz_d take 5, -5, 6, 8, 10). */
+ * Optional arguments are NULL / nord < 0 when absent.  hord: every order of xppm / yppm (:357-707) -- the linear schemes 1 .. 4
+ * (1 reads fv3_domain::lim_fac), the unlimited 5, 6, each of those negative (al = max(0, al) first; -5: the positive-definite
+ * adjustment on top), and 7 .. 13 (13 runs as 9).  0, -7 and below, 14 and above are refused; every entry point that takes an order
+ * (fv3_d_sw, fv3_update_dz_d, fv3_tracer_2d_step, fv3_d_sw_inline_q, fv3_ppm_line) takes this table and refuses with the same text.
+ * fx, fy must not alias an input or each other (refused: tiles write them while their neighbours still read q around the same faces). */
 int fv3_fv_tp_2d(fv3_ctx *ctx, int nk, const double *q, const double *crx, const double *cry, int hord,
                  double *fx, double *fy, const double *xfx, const double *yfx, const double *ra_x,
                  const double *ra_y, const double *mfx, const double *mfy, const double *mass, int nord,
@@ -156,8 +159,8 @@ int fv3_fv_tp_2d(fv3_ctx *ctx, int nk, const double *q, const double *crx, const
  * from the reference's docs/examples/tp_core.ipynb) go through it, iord 10 among them -- inside fv_tp_2d the inner sweep of hord 10 is
  * ord 8 (:136-141), so its vectors cannot pass through that entry unchanged.
  * h: the line with 3 halo cells on either side (n + 6), c: n + 1 Courant numbers, flux: n + 1 face values (device pointers).
- * which: 0 the operator of the LDS-tile kernels (every hord of fv3_fv_tp_2d), 1 / 2 the operators of the marching kernels along
- * the lanes (n <= 58) / through the register window (iord 5, -5, 6, 8, 10). */
+ * which: 0 the operator of the LDS-tile kernels, 1 / 2 the operators of the marching kernels along the lanes (n <= 58) / through
+ * the register window; every hord of fv3_fv_tp_2d in all three (hord 1 with the context's lim_fac: tests/golden/ppm1d_lin_golden.npz). */
 int fv3_ppm_line(fv3_ctx *ctx, int iord, int which, const double *h, const double *c, double *flux, int n);
 
 /* c_sw -- model/sw_core.F90:79-81, the k loop of model/dyn_core.F90:436-447.
@@ -171,7 +174,11 @@ int fv3_c_sw(fv3_ctx *ctx, double *delpc, const double *delp, double *ptc, const
              const double *v, const double *w, double *uc, double *vc, double *ua, double *va, double *wc,
              double *ut, double *vt, double *divg_d, int nord, double dt2, int hydrostatic, int dord4);
 
-/* Scalars of d_sw's argument list (model/sw_core.F90:494-500) that do not vary with k ... */
+/* Scalars of d_sw's argument list (model/sw_core.F90:494-500) that do not vary with k ...
+ * hord_vt, hord_tm, hord_dp (hord_tr: see fv3_d_sw_inline_q): the table of fv3_fv_tp_2d.  hord_mt (xtp_u / ytp_v, sw_core.F90:2154-2998):
+ * 1 .. 11 -- 1 .. 4 the linear schemes (:2245-2335; 1 reads lim_fac; 3 is NOT the scalar operator's 3), 5 .. 7, 8 .. 11; negative
+ * values are refused.  The fused marching kernels are built for hord_dp / hord_vt / hord_tm in 5, -5, 6, 8, 10 and hord_mt 5 .. 11; any
+ * other order runs the per-field marching kernels (doubly periodic) or the pass kernels over the whole face (cubed sphere). */
 typedef struct fv3_dsw_params {
   double dt;
   int hord_tr, hord_mt, hord_vt, hord_tm, hord_dp;
@@ -356,7 +363,7 @@ int fv3_riem_solver_c(fv3_ctx *ctx, double dt, const fv3_nh_consts *cn, const do
 /* update_dz_d -- model/nh_utils.F90:204, call site model/dyn_core.F90:911.  Uses the per-level nord_v /
  * damp_vt uploaded with fv3_dsw_levels_upload (entry npz+1 = entry npz, nh_utils.F90:240-241).
  * zh_in -> zh_out (A x (npz+1), compute domain written; must not alias); crx, xfx: CX x npz; cry, yfx:
- * CY x npz; zs: A; ws: CC. */
+ * CY x npz; zs: A; ws: CC.  hord (= hord_tm): as fv3_fv_tp_2d. */
 int fv3_update_dz_d(fv3_ctx *ctx, int hord, const double *zs, const double *zh_in, double *zh_out,
                     const double *crx, const double *cry, const double *xfx, const double *yfx, double *ws,
                     double rdt);
@@ -596,7 +603,8 @@ int fv3_tracer_2d_step(fv3_ctx *ctx, int it, int nsplt, const int *ksplt_host /*
  * call produced: crx, cry, xfx, yfx (crx_adv .. yfx_adv), fx / fy = the delp fluxes OF THIS SUBSTEP (hand fv3_d_sw zeroed arrays
  * as its mfx / mfy and add them to the accumulators with fv3_flux_accum), delp_old / delp_new = d_sw's delp and delp_out.  q (halo
  * updated, dyn_core.F90:341 / :573) -> q_out on the compute domain, A x npz x nq.  nord_t, damp_t: dyn_core.F90:690-692
- * (min(2, nord), vtdm4 with do_vort_damp): deln_flux with mass = d_sw's half-updated delp, sw_core.F90:1034. */
+ * (min(2, nord), vtdm4 with do_vort_damp): deln_flux with mass = d_sw's half-updated delp, sw_core.F90:1034.
+ * hord_tr: as fv3_fv_tp_2d. */
 int fv3_d_sw_inline_q(fv3_ctx *ctx, int nq, int hord_tr, int nord_t, double damp_t, const double *q, double *q_out,
                       const double *delp_old, const double *delp_new, const double *fx, const double *fy, const double *crx,
                       const double *cry, const double *xfx, const double *yfx);
