@@ -27,6 +27,7 @@
 #include "nh_kernels.h"
 #include "nh_fast.h"
 #include "nh_alt.h"
+#include "neg_adj.h"
 #include "remap_kernels.h"
 #include "remap_fast.h"
 #include "tracer_kernels.h"
@@ -4405,6 +4406,24 @@ extern "C" int fv3_fill2d_apply(fv3_ctx *c, int nk, const double *qt, const doub
   grid.y = 1;
   grid.z = (unsigned)nk;
   RT(launch_p(c, "fill2d_apply", grid, 0, kf));
+  return 0;
+}
+
+extern "C" int fv3_neg_adj3(fv3_ctx *c, const fv3_neg_adj_params *p, const double *peln, const double *delz, const double *delp,
+                            double *pt, double *qv, double *ql, double *qr, double *qi, double *qs, double *qg, double *qa) {
+  if (!c || !c->grid_ready) return fail("fv3_neg_adj3: context has no grid");
+  if (!p || !delp || !pt || !qv || !ql || !qr || !qi || !qs || !qg) return fail("fv3_neg_adj3: null parameters / field");
+  if (p->hydrostatic && !peln) return fail("fv3_neg_adj3: hydrostatic needs peln");
+  if (!p->hydrostatic && !delz) return fail("fv3_neg_adj3: nonhydrostatic needs delz");
+  const Grid &g = c->g;
+  if (g.npz < 2) return fail("fv3_neg_adj3: the vertical borrowing needs npz >= 2");
+  NegAdj3 kf{g, g.npz, p->hydrostatic ? 1 : 0, p->rdgas, p->rvgas, p->cp_air, p->cp_vapor, p->hlv, p->hlf, p->c_liq, p->c_ice,
+             delp, pt, qv, ql, qr, qi, qs, qg, qa};
+  Dim3 grid;
+  grid.x = (unsigned)(((size_t)g.nx * g.ny + NegAdj3::CH - 1) / NegAdj3::CH);
+  grid.y = 1;
+  grid.z = 1;
+  RT(launch_p(c, "neg_adj3", grid, 0, kf));
   return 0;
 }
 

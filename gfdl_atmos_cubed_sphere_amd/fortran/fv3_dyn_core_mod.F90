@@ -84,6 +84,11 @@ module fv3_arrays_compat_mod
     real(c_double) :: tau = 0.d0, rf_cutoff = 30.d2, fast_tau_w_sec = 0.d0
     logical :: RF_fast = .false., consv_am = .false., do_sat_adj = .false., moist_phys = .true.
     integer :: c2l_ord = 4, nwat = 3
+    ! the tail of fv_dynamics (fv_arrays.F90:627; fv_dynamics.F90:200-201, :264, :658-662, :722-745): the omega filter's passes, the
+    ! tracers at the end of the list that are not advected / not remapped (dnrts < 0: = dnats, as fv_control.F90:567 resolves it),
+    ! neg_adj3's report
+    integer :: nf_omega = 1, dnats = 0, dnrts = -1
+    logical :: check_negative = .false.
   end type
 
   type fv_nest_type
@@ -126,6 +131,9 @@ module fv3_arrays_compat_mod
   !> graupel): FMS reads the indices from the field table; here the host registers them (fv3_register_tracer_index) and fv_dynamics asks
   !> with the reference's own call.  An unregistered tracer is NO_TRACER (< 0, as FMS's).
   integer, parameter :: MODEL_ATMOS = 1, NO_TRACER = 1 - huge(1)
+  !> neg_adj3 runs whenever flagstruct%nwat == 6, as in the reference (fv_dynamics.F90:722).  .false. leaves it out: for a caller that
+  !> needs the results fv_dynamics gave before neg_adj3 was built (the solo drivers of the test-suite, unless FV3_REFSIG_NEG_ADJ=1)
+  logical, save :: fv3_compat_neg_adj = .true.
   integer, parameter, private :: max_tracers_compat = 64
   character(len=32), private :: tracer_names_compat(max_tracers_compat) = ' '
   integer, private :: tracer_index_compat(max_tracers_compat) = NO_TRACER, n_tracers_compat = 0
@@ -1002,7 +1010,7 @@ contains
     type(fv_thermo_type), intent(in) :: thermostruct
     type(fv3_flags), intent(inout) :: fl
     fl%use_cond = thermostruct%use_cond; fl%moist_kappa = thermostruct%moist_kappa
-    if (fl%use_cond .or. fl%moist_kappa) then
+    if (fl%use_cond .or. fl%moist_kappa .or. fl%neg_adj) then              ! (neg_adj3 reads the same indices, fv_dynamics.F90:727-733)
       fl%moist%nwat = int(flagstruct%nwat, c_int)
       fl%moist%sphum = int(max(0, get_tracer_index(MODEL_ATMOS, 'sphum')), c_int)
       fl%moist%liq_wat = int(max(0, get_tracer_index(MODEL_ATMOS, 'liq_wat')), c_int)
@@ -1010,7 +1018,7 @@ contains
       fl%moist%rainwat = int(max(0, get_tracer_index(MODEL_ATMOS, 'rainwat')), c_int)
       fl%moist%snowwat = int(max(0, get_tracer_index(MODEL_ATMOS, 'snowwat')), c_int)
       fl%moist%graupel = int(max(0, get_tracer_index(MODEL_ATMOS, 'graupel')), c_int)
-      if (fl%moist%sphum < 1) error stop 'fv_dynamics (fv3_dyn_core_mod): use_cond / moist_kappa need the index of sphum (fv3_register_tracer_index)'
+      if (fl%moist%sphum < 1) error stop 'fv_dynamics (fv3_dyn_core_mod): use_cond / moist_kappa / neg_adj3 need the index of sphum (fv3_register_tracer_index)'
       fl%moist%cv_vap = 3.d0 * 461.50d0; fl%moist%c_liq = 4.218d3; fl%moist%c_ice = 2.106d3
     end if
   end subroutine
@@ -1038,6 +1046,12 @@ contains
     fl%fast_tau_w_sec = flagstruct%fast_tau_w_sec; fl%RF_fast = flagstruct%RF_fast; fl%tau = flagstruct%tau
     fl%rf_cutoff = flagstruct%rf_cutoff
     fl%fill_dp = flagstruct%fill_dp                                        ! dyn_core.F90:820
+    fl%nf_omega = flagstruct%nf_omega                                      ! fv_dynamics.F90:658-662
+    fl%dnats = flagstruct%dnats; fl%dnrts = flagstruct%dnrts               ! :200-201, :264
+    if (fl%dnrts < 0) fl%dnrts = fl%dnats                                  ! fv_control.F90:567
+    fl%cld_amt = max(0, get_tracer_index(MODEL_ATMOS, 'cld_amt'))          ! :283, :571, :723
+    fl%check_negative = flagstruct%check_negative
+    fl%neg_adj = flagstruct%nwat == 6 .and. fv3_compat_neg_adj             ! :722
   end subroutine
 
   !> lazy = .true.: dyn_core (doubly periodic domain) copies a caller's array to the device only when the caller declared a write to it

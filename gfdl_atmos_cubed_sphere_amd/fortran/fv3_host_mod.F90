@@ -25,6 +25,7 @@ module fv3_host_mod
   public :: fv3_dyn_core, fv3_dyn_core_hydrostatic, fv3_tracer_2d, fv3_fv_dynamics, fv3_fv_dynamics_call
   public :: dmalloc, dzero, swap, upload_levels, host_n_con, KIND_A, KIND_U, KIND_V, KIND_B    ! shared with fv3_sphere_mod
   public :: inline_q_begin, inline_q_end, host_fast_tau_w, host_ray_fast, set_condensate, diss_est_begin
+  public :: host_remap_tracers, host_carry_unadvected, host_neg_adj3, host_negative_minima, host_print_negative, ptr_off
 
   integer(c_int), parameter :: KIND_A = 0, KIND_U = 1, KIND_V = 2, KIND_B = 3
   integer, parameter :: NG = 3
@@ -69,6 +70,15 @@ module fv3_host_mod
     ! flagstruct%fill_dp: mix_dp after d_sw (dyn_core.F90:820, :2119-2200) -- layers thinner than 1 % of their reference thickness take
     ! mass (and the w / pt that goes with it) from a neighbour; the reference thickness is that of the ak / bk given to fv3_host_init_grid
     logical :: fill_dp = .false.
+    ! the tail of fv_dynamics for moist runs.  neg_adj: neg_adj3 after the k_split loop (fv_dynamics.F90:722-745; the reference runs it
+    ! whenever nwat == 6), check_negative: its prt_negative report (fv_sg.F90:992-1002, :1323-1333).  nf_omega: passes of del2_cubed on
+    ! omga after the last remap (:658-662; the reference's default is 1).  dnats: the last dnats tracers are not advected (:200-201),
+    ! dnrts: the last dnrts are not remapped (< 0: = dnats, fv_control.F90:567).  cld_amt: index of the cloud fraction, 0 = absent:
+    ! remapped with kord 9 (:571), qa of neg_adj3.  All off: what the hosts did before they knew these.
+    logical :: neg_adj = .false., check_negative = .false.
+    integer :: nf_omega = 0, dnats = 0, dnrts = -1, cld_amt = 0
+    ! what neg_adj3 takes from constants_mod (rvgas, cp_vapor = 4 rvgas, hlv, hlf) and gfdl_mp_mod (c_liq, c_ice: gfdl_mp.F90:136-137)
+    real(c_double) :: rvgas = 461.50d0, cp_vapor = 4.d0 * 461.50d0, hlv = 2.500d6, hlf = 3.34d5, c_liq = 4.218d3, c_ice = 2.106d3
   end type
 
   !> device-resident state and work arrays of one rank (fv_atmos_type members + dyn_core.F90:256-283)
@@ -723,12 +733,101 @@ contains
     if (at%fl%trdm2 > 1.d-4) call halo(at, at%dp1, KIND_A, npz)                           ! dp1_pack, :466
     do it = 1, nsplt                                                                      ! :471-541
       call halo(at, at%q, KIND_A, npz * at%nq)                                            ! q_pack, :474 / :536
-      call fv3_check(fv3_tracer_2d_step(at%ctx, int(it, c_int), int(nsplt, c_int), ksplt, int(at%nq, c_int), &
+      call fv3_check(fv3_tracer_2d_step(at%ctx, int(it, c_int), int(nsplt, c_int), ksplt, int(at%nq - at%fl%dnats, c_int), &   ! nq_tot - dnats, :200
                                         int(at%fl%hord_tr, c_int), int(at%fl%nord_tr, c_int), at%fl%trdm2, at%q, at%q_n, &
                                         at%dp1, at%dp1_n, at%mfx, at%mfy, at%cx, at%cy, at%xfx, at%yfx), 'tracer_2d_step')
       call swap(at%q, at%q_n)
       if (it /= nsplt) call swap(at%dp1, at%dp1_n)
     end do
+    if (mod(nsplt, 2) == 1) call host_carry_unadvected(at)
+  end subroutine
+
+  !> p + n doubles
+  function ptr_off(p, n) result(r)
+    type(c_ptr), intent(in) :: p
+    integer(c_size_t), intent(in) :: n
+    type(c_ptr) :: r
+    r = transfer(transfer(p, 0_c_intptr_t) + int(n, c_intptr_t) * 8_c_intptr_t, r)
+  end function
+
+  !> the last dnats tracers from q_n to q after an odd number of swaps of the tracer ping-pong pair: tracer_2d leaves them where they were
+  subroutine host_carry_unadvected(at)
+    type(fv3_atmos), intent(inout) :: at
+    integer(c_size_t) :: off
+    if (at%fl%dnats <= 0) return
+    off = at%nA * int(at%npz, c_size_t) * int(at%nq - at%fl%dnats, c_size_t)
+    call fv3_check(fv3_memcpy_d2d(at%ctx, ptr_off(at%q, off), ptr_off(at%q_n, off), &
+                                  at%nA * int(at%npz, c_size_t) * int(at%fl%dnats, c_size_t) * 8_c_size_t), 'the tracers that are not advected')
+  end subroutine
+
+  !> nr = nq_tot - dnrts tracers are remapped (fv_dynamics.F90:264; dnrts < 0: = dnats, fv_control.F90:567), cld_amt with kord 9 (:569-572)
+  subroutine host_remap_tracers(fl, nq, nr, kord_tr)
+    type(fv3_flags), intent(in) :: fl
+    integer, intent(in) :: nq
+    integer, intent(out) :: nr
+    integer(c_int), allocatable, intent(out) :: kord_tr(:)
+    integer :: dnrts
+    dnrts = fl%dnrts
+    if (dnrts < 0) dnrts = fl%dnats
+    if (fl%dnats < 0 .or. fl%dnats > nq .or. dnrts > nq) error stop 'fv3_host_mod: dnats, dnrts must lie in 0 .. nq'
+    if (fl%cld_amt < 0 .or. fl%cld_amt > nq) error stop 'fv3_host_mod: cld_amt is not a tracer of 1 .. nq (0 = absent)'
+    if (fl%dnats > 0 .and. fl%inline_q) error stop 'fv3_host_mod: dnats > 0 with inline_q is not built (the inline tracers of d_sw take every tracer)'
+    nr = nq - dnrts
+    allocate(kord_tr(max(1, nq))); kord_tr = int(fl%kord_tr, c_int)
+    if (fl%cld_amt > 0 .and. fl%cld_amt <= nr) kord_tr(fl%cld_amt) = 9_c_int
+  end subroutine
+
+  !> prt_negative (fv_sg.F90:1372-1392) of T and the six species of one context: the minima (over the ranks of its communicator)
+  subroutine host_negative_minima(at, mins)
+    type(fv3_atmos), intent(inout) :: at
+    real(c_double), intent(out) :: mins(7)
+    real(c_double) :: out(3)
+    integer :: n, sp(6)
+    integer(c_size_t) :: n3
+    n3 = at%nA * int(at%npz, c_size_t)
+    sp = [int(at%fl%moist%sphum), int(at%fl%moist%liq_wat), int(at%fl%moist%rainwat), int(at%fl%moist%ice_wat), int(at%fl%moist%snowwat), &
+          int(at%fl%moist%graupel)]
+    call fv3_check(fv3_prt_maxmin(at%ctx, at%pt, int(at%npz, c_int), 1.d0, out), 'prt_negative')
+    mins(1) = out(2)
+    do n = 1, 6
+      call fv3_check(fv3_prt_maxmin(at%ctx, ptr_off(at%q, n3 * int(sp(n) - 1, c_size_t)), int(at%npz, c_int), 1.d0, out), 'prt_negative')
+      mins(n + 1) = out(2)
+    end do
+  end subroutine
+
+  subroutine host_print_negative(mins)
+    real(c_double), intent(in) :: mins(7)
+    character(len=11), parameter :: names(7) = [character(len=11) :: 'Temperature', 'sphum', 'liq_wat', 'rainwat', 'ice_wat', 'snowwat', 'graupel']
+    real(c_double), parameter :: thr(7) = [165.d0, -1.d-8, -1.d-7, -1.d-7, -1.d-7, -1.d-7, -1.d-7]       ! fv_sg.F90:994-1000
+    integer :: n
+    do n = 1, 7
+      if (mins(n) < thr(n)) write(*,*) trim(names(n)), ' min (negative) = ', mins(n)
+    end do
+  end subroutine
+
+  !> neg_adj3 (fv_sg.F90:968-1335) of one context, as fv_dynamics.F90:722-745 calls it: cld_amt as qa when that tracer exists
+  subroutine host_neg_adj3(at)
+    type(fv3_atmos), intent(inout) :: at
+    type(fv3_neg_adj_params) :: np
+    type(c_ptr) :: qa, peln, delz
+    integer(c_size_t) :: n3
+    if (at%fl%moist%nwat /= 6 .or. at%nq < 6) error stop 'fv3_host_mod: neg_adj is neg_adj3, the repair of six water species: nwat = 6'
+    if (min(at%fl%moist%sphum, at%fl%moist%liq_wat, at%fl%moist%rainwat, at%fl%moist%ice_wat, at%fl%moist%snowwat, at%fl%moist%graupel) < 1) &
+      error stop 'fv3_host_mod: neg_adj needs the tracer indices of the six water species (fl%moist)'
+    n3 = at%nA * int(at%npz, c_size_t)
+    np%hydrostatic = merge(1_c_int, 0_c_int, at%fl%hydrostatic)
+    np%rdgas = at%fl%rdgas; np%rvgas = at%fl%rvgas; np%grav = at%fl%grav; np%cp_air = at%fl%cp_air; np%cp_vapor = at%fl%cp_vapor
+    np%hlv = at%fl%hlv; np%hlf = at%fl%hlf; np%c_liq = at%fl%c_liq; np%c_ice = at%fl%c_ice
+    qa = c_null_ptr
+    if (at%fl%cld_amt > 0) qa = ptr_off(at%q, n3 * int(at%fl%cld_amt - 1, c_size_t))
+    peln = c_null_ptr; delz = at%delz
+    if (at%fl%hydrostatic) then
+      peln = at%peln; delz = c_null_ptr
+    end if
+    call fv3_check(fv3_neg_adj3(at%ctx, np, peln, delz, at%delp, at%pt, ptr_off(at%q, n3 * int(at%fl%moist%sphum - 1, c_size_t)), &
+                                ptr_off(at%q, n3 * int(at%fl%moist%liq_wat - 1, c_size_t)), ptr_off(at%q, n3 * int(at%fl%moist%rainwat - 1, c_size_t)), &
+                                ptr_off(at%q, n3 * int(at%fl%moist%ice_wat - 1, c_size_t)), ptr_off(at%q, n3 * int(at%fl%moist%snowwat - 1, c_size_t)), &
+                                ptr_off(at%q, n3 * int(at%fl%moist%graupel - 1, c_size_t)), qa), 'neg_adj3')
   end subroutine
 
   !> one dt_atmos: the k_split loop of fv_dynamics (fv_dynamics.F90:460-665): acoustic substeps, tracer transport,
@@ -741,10 +840,10 @@ contains
     type(fv3_remap_params) :: rp
     integer(c_int), allocatable :: kord_tr(:)
     real(c_double) :: mdt
-    integer :: n_map
+    integer :: n_map, nr
     mdt = bdt / real(at%fl%k_split, c_double)
-    allocate(kord_tr(max(1, at%nq))); kord_tr = int(at%fl%kord_tr, c_int)
-    rp%hydrostatic = merge(1_c_int, 0_c_int, at%fl%hydrostatic); rp%adiabatic = merge(1_c_int, 0_c_int, at%fl%adiabatic); rp%nq = int(at%nq, c_int)
+    call host_remap_tracers(at%fl, at%nq, nr, kord_tr)                                                     ! :264, :569-572
+    rp%hydrostatic = merge(1_c_int, 0_c_int, at%fl%hydrostatic); rp%adiabatic = merge(1_c_int, 0_c_int, at%fl%adiabatic); rp%nq = int(nr, c_int)
     rp%kord_mt = int(at%fl%kord_mt, c_int); rp%kord_wz = int(at%fl%kord_wz, c_int); rp%kord_tm = int(at%fl%kord_tm, c_int)
     rp%sphum = merge(1_c_int, 0_c_int, at%nq > 0); rp%fill = merge(1_c_int, 0_c_int, at%fl%fill)
     rp%akap = at%fl%akap; rp%ptop = at%fl%ptop; rp%rdgas = at%fl%rdgas; rp%grav = at%fl%grav
@@ -777,6 +876,15 @@ contains
                        'lagrangian_to_eulerian')                                                           ! :607
       end if
     end do
+    if (last_step .and. .not. present(last_code)) call omega_filter(at)      ! (with the energy fixer: after it, fv3_fv_dynamics_call)
+  end subroutine
+
+  !> del2_cubed(omga, 0.18 da_min, nf_omega) after the last remap (fv_dynamics.F90:658-662)
+  subroutine omega_filter(at)
+    type(fv3_atmos), intent(inout) :: at
+    if (at%fl%nf_omega <= 0) return
+    call halo(at, at%omga, KIND_A, at%npz)                                                                 ! del2_cubed's mpp_update_domains, dyn_core.F90:2399
+    call fv3_check(fv3_del2_cubed(at%ctx, at%omga, int(at%npz, c_int), 0.18d0 * at%da_min, int(at%fl%nf_omega, c_int)), 'del2_cubed (omga)')
   end subroutine
 
   !> A whole fv_dynamics call (model/fv_dynamics.F90:79-936 for the adiabatic core) on one doubly periodic tile (or this rank's block of
@@ -796,10 +904,13 @@ contains
     real(c_double) :: zv, zsum, dtmp, ph1, ph2
     logical :: hyd, fixer
     integer(c_int) :: ihyd
-    integer :: k
+    integer(c_int), allocatable :: kord_tr(:)
+    real(c_double) :: mins(7)
+    integer :: k, nr
     hyd = at%fl%hydrostatic; ihyd = merge(1_c_int, 0_c_int, hyd)
     fixer = abs(consv_te) > consv_min
-    rp%hydrostatic = ihyd; rp%adiabatic = merge(1_c_int, 0_c_int, at%fl%adiabatic); rp%nq = int(at%nq, c_int)
+    call host_remap_tracers(at%fl, at%nq, nr, kord_tr)
+    rp%hydrostatic = ihyd; rp%adiabatic = merge(1_c_int, 0_c_int, at%fl%adiabatic); rp%nq = int(nr, c_int)
     rp%kord_mt = int(at%fl%kord_mt, c_int); rp%kord_wz = int(at%fl%kord_wz, c_int); rp%kord_tm = int(at%fl%kord_tm, c_int)
     rp%sphum = merge(1_c_int, 0_c_int, at%nq > 0); rp%fill = merge(1_c_int, 0_c_int, at%fl%fill)
     rp%akap = at%fl%akap; rp%ptop = at%fl%ptop; rp%rdgas = at%fl%rdgas; rp%grav = at%fl%grav
@@ -884,8 +995,18 @@ contains
       end if
       at%dtmp = dtmp
       call fv3_check(fv3_remap_finish(at%ctx, rp, dtmp, at%pt, at%pkz, at%q), 'remap_finish')
+      call omega_filter(at)                                              ! :658-662
     else
       call fv3_fv_dynamics(at, bdt, .true.)
+    end if
+    if (at%fl%neg_adj) then                                              ! :722-745
+      if (at%fl%check_negative) then
+        call host_negative_minima(at, mins); call host_print_negative(mins)
+      end if
+      call host_neg_adj3(at)
+      if (at%fl%check_negative) then
+        call host_negative_minima(at, mins); call host_print_negative(mins)
+      end if
     end if
     if (at%consv_am) call consv_am_correct()                             ! :747-800
     if (c2l_ord == 4) then                                               ! fv_grid_utils.F90:2372-2376

@@ -24,6 +24,7 @@ module fv3_mi355x_mod
   public :: fv3_cube_field, fv3_cube_table, fv3_cube_halo_start, fv3_cube_halo_complete
   public :: FV3_CUBE_A, FV3_CUBE_B, FV3_CUBE_D, FV3_CUBE_C, FV3_CUBE_DEDGE
   public :: fv3_c2l, fv3_rayleigh_u2f, fv3_rayleigh_apply, fv3_rayleigh_super, fv3_compute_total_energy, fv3_energy_fixer_sums, fv3_remap_finish, fv3_ordered_sum, fv3_adv_pe, fv3_set_condensate, fv3_registry_mode, fv3_registry_put, fv3_registry_get, fv3_registry_host_touched, fv3_registry_fetch, fv3_registry_forget, fv3_registry_stats, fv3_set_fast_tau_w, fv3_set_ray_fast, fv3_ray_fast, fv3_mix_dp, fv3_compute_aam, fv3_consv_am_apply, fv3_set_moist, fv3_moist_params
+  public :: fv3_neg_adj3, fv3_neg_adj_params
 
   type, bind(C) :: fv3_domain
     integer(c_int) :: is, ie, js, je, ng, npx, npy, npz, grid_type
@@ -81,6 +82,11 @@ module fv3_mi355x_mod
   type, bind(C) :: fv3_moist_params   ! moist_kappa / use_cond of the remap + the inputs of moist_cv
     integer(c_int) :: moist_kappa, use_cond, nwat, sphum, liq_wat, rainwat, ice_wat, snowwat, graupel
     real(c_double) :: cv_vap, c_liq, c_ice
+  end type
+
+  type, bind(C) :: fv3_neg_adj_params ! neg_adj3 (fv_sg.F90:968): the mode and the caller's constants_mod / gfdl_mp_mod values
+    integer(c_int) :: hydrostatic
+    real(c_double) :: rdgas, rvgas, grav, cp_air, cp_vapor, hlv, hlf, c_liq, c_ice
   end type
 
   type, bind(C) :: fv3_remap_params   ! Lagrangian_to_Eulerian scalars (fv_mapz.F90:56-64)
@@ -629,6 +635,13 @@ module fv3_mi355x_mod
       import :: c_int, c_ptr, fv3_moist_params
       type(c_ptr), value :: ctx, q_con, cappa
       type(fv3_moist_params), intent(in) :: m
+    end function
+    ! neg_adj3 (fv_sg.F90:968-1335, call site fv_dynamics.F90:722-745); the species are c_loc(q(isd,jsd,1,iq)), qa = c_null_ptr
+    ! without cld_amt, delz = c_null_ptr when hydrostatic (then peln is needed)
+    integer(c_int) function fv3_neg_adj3(ctx, p, peln, delz, delp, pt, qv, ql, qr, qi, qs, qg, qa) bind(C, name="fv3_neg_adj3")
+      import :: c_int, c_ptr, fv3_neg_adj_params
+      type(c_ptr), value :: ctx, peln, delz, delp, pt, qv, ql, qr, qi, qs, qg, qa
+      type(fv3_neg_adj_params), intent(in) :: p
     end function
     integer(c_int) function fv3_set_ak_bk(ctx, ak, bk) bind(C, name="fv3_set_ak_bk")
       import :: c_int, c_ptr, c_double

@@ -17,7 +17,7 @@ program fv3_solo_refsig
   type(fv_atmos_type), pointer :: parent_grid => null()
   type(inline_mp_type) :: inline_mp
   real(c_double), allocatable :: ps(:,:), u0(:,:,:), v0(:,:,:), ze0(:,:,:)
-  logical :: whole, hyb_z
+  logical :: whole, hyb_z, with_omga
   integer(c_long_long) :: tc0, tc1, tcr
   integer(c_int) :: nx, ny, npz, nq, n_split, k_split, nsteps, last_step, ihydro
   real(c_double) :: dxc_, dyc_, f0_, bdt, ptop, d_con, d_ext, beta, consv_te, tau
@@ -179,6 +179,20 @@ program fv3_solo_refsig
   ! FV3_REFSIG_FILL_DP=1: flagstruct%fill_dp (mix_dp after d_sw, with the file's ak / bk as the reference thicknesses)
   call get_environment_variable('FV3_REFSIG_FILL_DP', envbuf, status=envstat)
   if (envstat == 0 .and. trim(envbuf) == '1') fs%fill_dp = .true.
+  ! the tail of fv_dynamics stays as this driver always ran it -- no omega filter, no neg_adj3, every tracer advected and remapped --
+  ! unless the environment asks: FV3_REFSIG_NF_OMEGA=<n> (flagstruct%nf_omega; omga then joins the output, last), FV3_REFSIG_NEG_ADJ=1
+  ! (neg_adj3 as the reference runs it for nwat = 6), FV3_REFSIG_DNATS=<n> (flagstruct%dnats; the last tracer is then cld_amt)
+  fs%nf_omega = 0; fv3_compat_neg_adj = .false.
+  call get_environment_variable('FV3_REFSIG_NF_OMEGA', envbuf, status=envstat)
+  with_omga = envstat == 0 .and. len_trim(envbuf) > 0
+  if (with_omga) read(envbuf, *) fs%nf_omega
+  call get_environment_variable('FV3_REFSIG_NEG_ADJ', envbuf, status=envstat)
+  if (envstat == 0 .and. trim(envbuf) == '1') fv3_compat_neg_adj = .true.
+  call get_environment_variable('FV3_REFSIG_DNATS', envbuf, status=envstat)
+  if (envstat == 0 .and. len_trim(envbuf) > 0) then
+    read(envbuf, *) fs%dnats
+    if (fs%dnats > 0) call fv3_register_tracer_index('cld_amt', int(nq))
+  end if
 
   if (whole) then
     fs%c2l_ord = 4; fs%tau = tau; fs%moist_phys = .false.
@@ -208,6 +222,7 @@ program fv3_solo_refsig
     write(un) ua
     if (moist) write(un) q_con
     if (fs%do_diss_est) write(un) diss_est
+    if (with_omga) write(un) omga
     close(un)
     write(*,'(a,es24.16)') 'fv3_solo_refsig: done, sum(delp) = ', sum(delp(1:nx, 1:ny, :))
     stop

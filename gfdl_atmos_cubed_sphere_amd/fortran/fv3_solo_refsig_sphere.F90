@@ -45,7 +45,9 @@ program fv3_solo_refsig_sphere
   type(fv_atmos_type), pointer :: parent => null()
   type(inline_mp_type) :: imp
   real(c_double), allocatable :: a9(:,:,:), u9(:,:,:), v9(:,:,:), b4(:,:,:), a4(:,:,:), ec(:,:,:,:), en1(:,:,:), en2(:,:,:)
-  logical :: hydrostatic, moist
+  logical :: hydrostatic, moist, with_omga
+  character(len=64) :: envbuf
+  integer :: envstat
   integer :: un, t, nx, isd, ied, c
 
   call get_command_argument(1, fin)
@@ -139,6 +141,21 @@ program fv3_solo_refsig_sphere
     call fv3_register_tracer_index('rainwat', 3); call fv3_register_tracer_index('ice_wat', 4)
     call fv3_register_tracer_index('snowwat', 5); call fv3_register_tracer_index('graupel', 6)
   end if
+  ! the tail of fv_dynamics stays as this driver always ran it -- no omega filter, no neg_adj3, every tracer advected and remapped --
+  ! unless the environment asks: FV3_REFSIG_NF_OMEGA=<n> (flagstruct%nf_omega; omga then joins every tile's output, last),
+  ! FV3_REFSIG_NEG_ADJ=1 (neg_adj3 as the reference runs it for nwat = 6), FV3_REFSIG_DNATS=<n> (flagstruct%dnats; the last tracer is
+  ! then cld_amt)
+  fl%nf_omega = 0; fv3_compat_neg_adj = .false.
+  call get_environment_variable('FV3_REFSIG_NF_OMEGA', envbuf, status=envstat)
+  with_omga = envstat == 0 .and. len_trim(envbuf) > 0
+  if (with_omga) read(envbuf, *) fl%nf_omega
+  call get_environment_variable('FV3_REFSIG_NEG_ADJ', envbuf, status=envstat)
+  if (envstat == 0 .and. trim(envbuf) == '1') fv3_compat_neg_adj = .true.
+  call get_environment_variable('FV3_REFSIG_DNATS', envbuf, status=envstat)
+  if (envstat == 0 .and. len_trim(envbuf) > 0) then
+    read(envbuf, *) fl%dnats
+    if (fl%dnats > 0) call fv3_register_tracer_index('cld_amt', int(nq))
+  end if
   dom%pe = rank; dom%npes = nranks; dom%face_rank = face_rank; dom%comm_id = comm_id
   allocate(pfull(npz), te0(nx, nx), cappa(1,1,1)); pfull = 0.d0; te0 = 0.d0
   do t = 1, 6
@@ -171,6 +188,11 @@ program fv3_solo_refsig_sphere
     if (moist) write(un) st(t)%qcon
     if (fl%do_diss_est) write(un) st(t)%diss
   end do
+  if (with_omga) then                 ! after every tile's block, so that a reader of the blocks finds them where they were
+    do t = 1, 6
+      if (face_rank(t) == rank) write(un) st(t)%omga
+    end do
+  end if
   close(un)
   call fv_dynamics_end()
   call dyn_core_end()

@@ -140,6 +140,7 @@ contains
     case (14); p = at%phis
     case (15); p = at%q_con
     case (16); p = at%cappa
+    case (17); p = at%omga
     case default; p = c_null_ptr
     end select
   end function
@@ -401,7 +402,7 @@ contains
       call exchange(sp, 1, [FV3_CUBE_A + 0], [12], [0], [npz * nq])                         ! q_pack, :474 / :536
       do i = 1, sp%nf
         associate (at => sp%f(i))
-          call fv3_check(fv3_tracer_2d_step(at%ctx, int(it, c_int), int(nsplt, c_int), ksplt, int(nq, c_int), &
+          call fv3_check(fv3_tracer_2d_step(at%ctx, int(it, c_int), int(nsplt, c_int), ksplt, int(nq - fl%dnats, c_int), &   ! nq_tot - dnats, :200
                                             int(fl%hord_tr, c_int), int(fl%nord_tr, c_int), fl%trdm2, at%q, at%q_n, &
                                             at%dp1, at%dp1_n, at%mfx, at%mfy, at%cx, at%cy, at%xfx, at%yfx), 'tracer_2d_step')
           call swap(at%q, at%q_n)
@@ -409,6 +410,11 @@ contains
         end associate
       end do
     end do
+    if (mod(nsplt, 2) == 1) then
+      do i = 1, sp%nf
+        call host_carry_unadvected(sp%f(i))
+      end do
+    end if
   end subroutine
 
   !> one dt_atmos: the k_split loop of fv_dynamics (fv_dynamics.F90:460-665) on the faces of this rank.  pt holds theta_v;
@@ -422,13 +428,13 @@ contains
     type(fv3_remap_params) :: rp
     integer(c_int), allocatable :: kord_tr(:)
     real(c_double) :: mdt
-    integer :: n_map, i, nq
+    integer :: n_map, i, nq, nr
     type(fv3_flags) :: fl
     fl = sp%f(1)%fl
     nq = sp%f(1)%nq
     mdt = bdt / real(fl%k_split, c_double)
-    allocate(kord_tr(max(1, nq))); kord_tr = int(fl%kord_tr, c_int)
-    rp%hydrostatic = merge(1_c_int, 0_c_int, fl%hydrostatic); rp%adiabatic = merge(1_c_int, 0_c_int, fl%adiabatic); rp%nq = int(nq, c_int)
+    call host_remap_tracers(fl, nq, nr, kord_tr)                                                                  ! :264, :569-572
+    rp%hydrostatic = merge(1_c_int, 0_c_int, fl%hydrostatic); rp%adiabatic = merge(1_c_int, 0_c_int, fl%adiabatic); rp%nq = int(nr, c_int)
     rp%kord_mt = int(fl%kord_mt, c_int); rp%kord_wz = int(fl%kord_wz, c_int); rp%kord_tm = int(fl%kord_tm, c_int)
     rp%sphum = merge(1_c_int, 0_c_int, nq > 0); rp%fill = merge(1_c_int, 0_c_int, fl%fill)
     rp%akap = fl%akap; rp%ptop = fl%ptop; rp%rdgas = fl%rdgas; rp%grav = fl%grav
@@ -465,6 +471,20 @@ contains
           end if
         end associate
       end do
+    end do
+    if (last_step .and. .not. present(last_code)) call sphere_omega_filter(sp)   ! (with the energy fixer: after it, fv3_sphere_fv_dynamics_call)
+  end subroutine
+
+  !> del2_cubed(omga, 0.18 da_min, nf_omega) after the last remap (fv_dynamics.F90:658-662)
+  subroutine sphere_omega_filter(sp)
+    type(fv3_sphere), intent(inout) :: sp
+    integer :: i
+    if (sp%f(1)%fl%nf_omega <= 0) return
+    call exchange(sp, 1, [FV3_CUBE_A + 0], [17], [0], [sp%f(1)%npz])                                              ! del2_cubed's mpp_update_domains, dyn_core.F90:2399
+    do i = 1, sp%nf
+      associate (at => sp%f(i))
+        call fv3_check(fv3_del2_cubed(at%ctx, at%omga, int(at%npz, c_int), 0.18d0 * at%da_min, int(at%fl%nf_omega, c_int)), 'del2_cubed (omga)')
+      end associate
     end do
   end subroutine
 
@@ -578,8 +598,16 @@ contains
       do i = 1, sp%nf
         call fv3_check(fv3_remap_finish(sp%f(i)%ctx, rp, dtmp, sp%f(i)%pt, sp%f(i)%pkz, sp%f(i)%q), 'remap_finish')
       end do
+      call sphere_omega_filter(sp)                           ! :658-662
     else
       call fv3_sphere_fv_dynamics(sp, bdt, .true., nranks)
+    end if
+    if (fl%neg_adj) then                                     ! :722-745
+      if (fl%check_negative) call sphere_prt_negative()
+      do i = 1, sp%nf
+        call host_neg_adj3(sp%f(i))
+      end do
+      if (fl%check_negative) call sphere_prt_negative()
     end if
     if (sp%f(1)%consv_am) call consv_am_correct()            ! :747-800
     if (c2l_ord == 4) call exchange(sp, 1, [FV3_CUBE_D + 0], [1], [2], [npz])                  ! fv_grid_utils.F90:2372-2376
@@ -588,6 +616,21 @@ contains
     end do
 
   contains
+
+    !> prt_negative (fv_sg.F90:1372-1392): the minima over the faces of this rank (and, inside fv3_prt_maxmin, over the ranks)
+    subroutine sphere_prt_negative()
+      real(c_double) :: mins(7), m1(7)
+      integer :: j
+      do j = 1, sp%nf
+        call host_negative_minima(sp%f(j), m1)
+        if (j == 1) then
+          mins = m1
+        else
+          mins = min(mins, m1)
+        end if
+      end do
+      call host_print_negative(mins)
+    end subroutine
 
     !> compute_aam (fv_dynamics.F90:1266-1314) of every face: cubed_to_latlon (mode 1, c2l_ord 2: no halo update), then aam, m_fac, ps
     !> of every column; first: into teq / ps2 (the state the step starts from), else into the work array / ps
@@ -709,7 +752,9 @@ contains
     type(fv3_remap_params), intent(out) :: rp
     type(fv3_flags) :: fl
     integer :: nq
-    fl = sp%f(1)%fl; nq = sp%f(1)%nq
+    integer(c_int), allocatable :: kord_tr(:)
+    fl = sp%f(1)%fl
+    call host_remap_tracers(fl, sp%f(1)%nq, nq, kord_tr)       ! nr = nq_tot - dnrts, as Lagrangian_to_Eulerian is handed it (:264, :609)
     rp%hydrostatic = merge(1_c_int, 0_c_int, fl%hydrostatic); rp%adiabatic = merge(1_c_int, 0_c_int, fl%adiabatic); rp%nq = int(nq, c_int)
     rp%kord_mt = int(fl%kord_mt, c_int); rp%kord_wz = int(fl%kord_wz, c_int); rp%kord_tm = int(fl%kord_tm, c_int)
     rp%sphum = merge(1_c_int, 0_c_int, nq > 0); rp%fill = merge(1_c_int, 0_c_int, fl%fill)

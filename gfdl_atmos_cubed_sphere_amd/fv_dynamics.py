@@ -6,19 +6,33 @@ the sub-cycled tracer transport (``tracer_2d``) and the vertical remap (``Lagran
 ``fv_dynamics`` call on a Cartesian domain or on the six faces of the sphere: compute_total_energy when consv_te > 0 (:345), T ->
 theta_v / theta_m (fv_dynamics.F90:296-399, with moist_cv under use_cond / moist_kappa), the Rayleigh damping when tau > 0
 (:362-371: Rayleigh_Super on the cubed sphere and in ideal cases, Rayleigh_Friction otherwise), the k_split loop, the energy
-fixer and theta_v -> T in the last remap, cubed_to_latlon (:911).  The angular-momentum fixer (consv_am), nudging and the
-diagnostics (:669-803) are not built.
+fixer and theta_v -> T in the last remap, the filter of omega (:658-662, nf_omega), neg_adj3 (:722-745, neg_adj), the angular-momentum
+fixer (:747-800, consv_am), cubed_to_latlon (:911).  Tracers that are not advected or not remapped (dnats, dnrts, :200-201, :264) and
+cld_amt's own remap order (:569-572) follow the reference.  Nudging and the diagnostics are not built.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from .dyn_core import DynCore, DynFlags
-from .lib import CP_AIR, Context
+from .lib import CP_AIR, NEG_ADJ_CONSTS, Context
 from .tracer2d import tracer_2d
 
 
 CONSV_MIN = 0.001   # fv_mapz.F90:45: below it no correction applies
+# prt_negative's names and thresholds at fv_sg.F90:994-1000: T below, the species below
+NEGATIVE_THRESHOLDS = (("Temperature", 165.0), ("sphum", -1.0e-8), ("liq_wat", -1.0e-7), ("rainwat", -1.0e-7), ("ice_wat", -1.0e-7),
+                       ("snowwat", -1.0e-7), ("graupel", -1.0e-7))
+
+
+class _TracerView:
+    """one tracer (A x npz) of a tracer array on the device, for the entry points that take a field"""
+
+    def __init__(self, q, iq: int):
+        import ctypes as C
+        self.shape = tuple(q.shape[:3])
+        self.ptr = q.ptr + 8 * int(np.prod(self.shape)) * iq
+        self.p = C.cast(C.c_void_p(self.ptr), C.POINTER(C.c_double))
 
 
 class FvDynamics:
@@ -27,7 +41,8 @@ class FvDynamics:
                  px: int = 1, py: int = 1, rank: int = 0, world: int = 1, dist=None, tau: float = 0.0,
                  rf_cutoff: float = 30.0e2, c2l_ord: int = 4, moist: dict | None = None, fill: bool = False, halo=None,
                  consv_te: float = 0.0, moist_phys: bool = False, radius: float = 6.3712e6, fill2d: tuple = (),
-                 remap_te: bool = False, consv_am: dict | None = None):
+                 remap_te: bool = False, consv_am: dict | None = None, neg_adj: bool = False, check_negative: bool = False,
+                 nf_omega: int = 0, dnats: int = 0, dnrts: int = -1, cld_amt: int = 0, neg_adj_consts: dict | None = None):
         ak, bk = np.asarray(ak, dtype=np.float64), np.asarray(bk, dtype=np.float64)
         dp_ref = (ak[1:] - ak[:-1]) + (bk[1:] - bk[:-1]) * 1.0e5          # dyn_core.F90:241-244
         # flagstruct%tau / %rf_cutoff are ONE pair in the reference: Rayleigh_Friction / _Super here (fv_dynamics.F90:362-376) and Ray_fast /
@@ -45,6 +60,31 @@ class FvDynamics:
         flags = dataclasses.replace(flags, tau=tau, rf_cutoff=rf_cutoff)
         self.ctx, self.fl, self.nq, self.k_split, self.q_split, self.dist = ctx, flags, nq, k_split, q_split, dist
         self.nord_tr, self.trdm2 = nord_tr, trdm2
+        # the tail of fv_dynamics for moist runs.  neg_adj: neg_adj3 after the k_split loop (fv_dynamics.F90:722-745; the reference runs
+        # it whenever nwat == 6), check_negative: its prt_negative report (fv_sg.F90:992-1002, :1323-1333), neg_adj_consts: overrides of
+        # lib.NEG_ADJ_CONSTS.  nf_omega: passes of del2_cubed on omga after the last remap (:658-662; the reference's default is 1).
+        # dnats: the last dnats tracers are not advected (:200-201), dnrts: the last dnrts are not remapped (< 0: = dnats,
+        # fv_control.F90:567).  cld_amt: 1-based index of the cloud fraction, 0 = absent: remapped with kord 9 (:571), qa of neg_adj3.
+        if dnrts < 0:
+            dnrts = dnats
+        if not 0 <= dnats <= nq or not 0 <= dnrts <= nq:
+            raise ValueError(f"FvDynamics: dnats = {dnats}, dnrts = {dnrts} must lie in 0..nq = {nq}")
+        if not 0 <= cld_amt <= nq:
+            raise ValueError(f"FvDynamics: cld_amt = {cld_amt} is not a tracer of 1..{nq} (0 = absent)")
+        if neg_adj and (moist or {}).get("nwat", 0) != 6:
+            raise ValueError("FvDynamics: neg_adj is neg_adj3, the repair of the six water species: it needs moist['nwat'] == 6")
+        if dnats and flags.inline_q:
+            raise ValueError("FvDynamics: dnats > 0 with inline_q is not built (d_sw's inline tracers take every tracer)")
+        if nf_omega < 0:
+            raise ValueError(f"FvDynamics: nf_omega = {nf_omega}")
+        self.neg_adj, self.check_negative, self.nf_omega = bool(neg_adj), bool(check_negative), int(nf_omega)
+        self.dnats, self.dnrts, self.cld_amt = int(dnats), int(dnrts), int(cld_amt)
+        self.neg_adj_consts = dict(NEG_ADJ_CONSTS, rdgas=flags.rdgas, grav=flags.grav, cp_air=flags.cp_air, **(neg_adj_consts or {}))
+        # the tracer indices (1-based) of the six species: the moist dict's, by default the first six in the reference's usual order
+        self.neg_adj_species = tuple(int((moist or {}).get(n, k + 1))
+                                     for k, n in enumerate(("sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel")))
+        self.rank = rank
+        self.negative_report = []          # check_negative: (when, name, minimum) of what fell below its threshold
         # fill2D (fv_dynamics.F90:542-556, FILL2D builds): the 0-based tracer indices of liq_wat, rainwat, ice_wat, snowwat, graupel
         # that get the diffusive filling after tracer_2d when hord_tr < 8 and moist_phys
         self.fill2d = tuple(int(i) for i in fill2d)
@@ -82,6 +122,12 @@ class FvDynamics:
                               kord_tm=kord_tm, sphum=1 if nq else 0, akap=flags.akap, ptop=flags.ptop,
                               rdgas=flags.rdgas, grav=flags.grav, cv_air=flags.cp_air - flags.rdgas, r_vir=0.6077,
                               cp=flags.cp_air, t_min=184.0, kord_tr=[kord_tr] * nq, fill=int(fill))
+        nr = nq - self.dnrts                                               # :264, :569-572
+        if nr != nq or (0 < self.cld_amt <= nr):
+            kt = [kord_tr] * nr
+            if 0 < self.cld_amt <= nr:
+                kt[self.cld_amt - 1] = 9
+            self.remap_par.update(nq=nr, kord_tr=kt)
 
     def set_tracers(self, q: np.ndarray):
         self.dc.d["q"].upload(q)
@@ -109,9 +155,56 @@ class FvDynamics:
         else:
             conv(int(fl.hydrostatic))
         self.step(bdt, last_cycle_is_last_step=True)
+        if self.neg_adj:                                                   # :722-745
+            self._neg_adj3()
         if self.consv_am:                                                  # :747-800
             self._consv_am(bdt)
         self.cubed_to_latlon()                                             # :911
+
+    # -- neg_adj3 -------------------------------------------------------------------------------------------------
+    def _prt_negative(self, when: str):
+        """prt_negative (fv_sg.F90:1372-1392) of T and the six species: the global minimum, reported when below its threshold"""
+        d, ctx = self.dc.d, self.ctx
+        multi = hasattr(ctx, "ctxs")
+        for n, (name, thr) in enumerate(NEGATIVE_THRESHOLDS):
+            if n == 0:
+                f = d["pt"]
+            elif multi:
+                from .cubed_dyn import FaceSet
+                f = FaceSet([_TracerView(a, self.neg_adj_species[n - 1] - 1) for a in d["q"].a])
+            else:
+                f = _TracerView(d["q"], self.neg_adj_species[n - 1] - 1)
+            out = ctx.prt_maxmin(f, 1.0)
+            qmin = min(o[1] for o in out) if multi else out[1]
+            if self.dist is not None:                                      # mp_reduce_min over the ranks of the host's process group
+                import torch
+                t = torch.tensor([qmin], dtype=torch.float64)
+                if self.dist.get_backend() == "nccl":
+                    t = t.cuda()
+                self.dist.all_reduce(t, op=self.dist.ReduceOp.MIN)
+                qmin = float(t.cpu()[0])
+            if qmin < thr:
+                self.negative_report.append((when, name, qmin))
+                if self.rank == 0:
+                    print(f" {name} min (negative) = {qmin!r}")
+
+    def _neg_adj3(self):
+        d, ctx, hyd = self.dc.d, self.ctx, self.fl.hydrostatic
+        if self.check_negative:
+            self._prt_negative("before")
+        ctx.neg_adj3(hyd, d["peln"] if hyd else None, None if hyd else d["delz"], d["delp"], d["pt"], d["q"],
+                     species=self.neg_adj_species, qa=self.cld_amt, consts=self.neg_adj_consts)
+        if self.check_negative:
+            self._prt_negative("after")
+
+    def _carry_unadvected(self, dst, src):
+        """the last dnats tracers from one buffer of the tracer ping-pong pair to the other: tracer_2d leaves them where they were"""
+        import ctypes as C
+        nadv = self.nq - self.dnats
+        for a, b in zip(getattr(dst, "a", [dst]), getattr(src, "a", [src])):
+            n3 = int(np.prod(a.shape[:3]))
+            a.ctx.lib.check(a.ctx.lib.dll.fv3_memcpy_d2d(a.ctx.h, C.c_void_p(a.ptr + 8 * n3 * nadv), C.c_void_p(b.ptr + 8 * n3 * nadv),
+                                                         C.c_size_t(8 * n3 * self.dnats)), "fv3_memcpy_d2d")
 
     # -- consv_am -------------------------------------------------------------------------------------------------
     def _aam(self, aam_name: str, ps_name: str):
@@ -277,9 +370,11 @@ class FvDynamics:
             self.dc.run(mdt, end_step=(n_map == self.k_split))                 # :493, last_step = (n_map == k_split)
             if self.nq and not self.fl.inline_q:                               # :509-533 (inline_q: the tracers rode inside d_sw)
                 q, dp1, _ = tracer_2d(ctx, self.dc.halo, d["q"], d["q_nxt"], d["dp1"], d["dp1_nxt"], d["mfx"], d["mfy"],
-                                      d["cx"], d["cy"], d["crx"], d["cry"], self.nq, self.fl.hord_tr, self.q_split,
-                                      self.nord_tr, self.trdm2, dist=self.dist)
+                                      d["cx"], d["cy"], d["crx"], d["cry"], self.nq - self.dnats, self.fl.hord_tr, self.q_split,
+                                      self.nord_tr, self.trdm2, dist=self.dist)          # nq = nq_tot - dnats, :200
                 if q is not d["q"]:
+                    if self.dnats:
+                        self._carry_unadvected(d["q_nxt"], d["q"])
                     d["q"], d["q_nxt"] = d["q_nxt"], d["q"]
                 if dp1 is not d["dp1"]:
                     d["dp1"], d["dp1_nxt"] = d["dp1_nxt"], d["dp1"]
@@ -297,3 +392,6 @@ class FvDynamics:
                                        d["peln"], d["omga"], None if hyd else d["ws"])   # :607
             if fixer:
                 self._energy_fixer(par, bdt)
+            if last_step and self.nf_omega > 0:                                # :658-662
+                self.dc.halo.update([(d["omga"], "A")])                        # del2_cubed's mpp_update_domains, dyn_core.F90:2399
+                ctx.del2_cubed(d["omga"], 0.18 * ctx.grid.da_min, self.nf_omega)

@@ -36,7 +36,7 @@ EXPORTS = ["fv3_last_error", "fv3_create", "fv3_destroy", "fv3_set_stream", "fv3
            "fv3_halo_unpack", "fv3_pt_to_theta_v", "fv3_c2l", "fv3_rayleigh_u2f", "fv3_rayleigh_apply", "fv3_rayleigh_super", "fv3_compute_total_energy", "fv3_energy_fixer_sums", "fv3_remap_finish", "fv3_ordered_sum", "fv3_adv_pe", "fv3_omga_update", "fv3_divg2_ext", "fv3_one_grad_p", "fv3_one_grad_p_nh", "fv3_copy_a_to_cc", "fv3_heat_source_accum", "fv3_del2_cubed", "fv3_apply_heat_source", "fv3_profile", "fv3_profile_report", "fv3_comm_get_unique_id", "fv3_comm_init", "fv3_comm_destroy", "fv3_halo_start", "fv3_halo_complete", "fv3_allreduce_max", "fv3_cube_table", "fv3_cube_halo_start", "fv3_cube_halo_complete",
            "fv3_set_dp_ref", "fv3_update_dz_c", "fv3_set_condensate", "fv3_set_fast_tau_w", "fv3_set_ray_fast", "fv3_ray_fast", "fv3_mix_dp", "fv3_compute_aam", "fv3_consv_am_apply", "fv3_riem_solver_c", "fv3_update_dz_d", "fv3_riem_solver3",
            "fv3_p_grad_c", "fv3_nh_p_grad", "fv3_split_p_grad", "fv3_grad1_p_update", "fv3_d_sw_inline_q", "fv3_flux_accum", "fv3_fill2d_mass", "fv3_fill2d_apply", "fv3_set_remap_te", "fv3_profile_report_timers", "fv3_prt_maxmin", "fv3_pk3_halo", "fv3_pe_halo", "fv3_geopk", "fv3_zh_from_delz", "fv3_set_ak_bk", "fv3_set_moist", "fv3_lagrangian_to_eulerian",
-           "fv3_tracer_2d_prep", "fv3_tracer_2d_scale", "fv3_tracer_2d_step"]
+           "fv3_tracer_2d_prep", "fv3_tracer_2d_scale", "fv3_tracer_2d_step", "fv3_neg_adj3"]
 
 
 class Fv3Error(RuntimeError):
@@ -122,6 +122,16 @@ class _NhConsts(C.Structure):
 # FMS constants_mod (GFDL defaults, FMS 2024.03 constants/gfdl_constants.fh): not in the reference tree
 GRAV, RDGAS, KAPPA = 9.80, 287.04, 2.0 / 7.0
 CP_AIR = RDGAS / KAPPA
+# what neg_adj3 (fv_sg.F90:968) takes from its host modules, the defaults of Context.neg_adj3 / FvDynamics(neg_adj_consts=...)
+NEG_ADJ_CONSTS = dict(
+    rdgas=RDGAS, grav=GRAV, cp_air=CP_AIR,   # constants_mod, as above
+    rvgas=461.50,       # constants_mod RVGAS (gfdl_constants.fh)
+    cp_vapor=4.0 * 461.50,   # constants_mod CP_VAPOR = 4 * RVGAS
+    hlv=2.500e6,        # constants_mod HLV
+    hlf=3.34e5,         # constants_mod HLF
+    c_liq=4.218e3,      # gfdl_mp_mod c_liq (model/gfdl_mp.F90:137, used by fv_sg.F90:34): heat capacity of water at 0 deg C
+    c_ice=2.106e3,      # gfdl_mp_mod c_ice (model/gfdl_mp.F90:136): heat capacity of ice at 0 deg C
+)
 
 
 def nh_consts(ptop, p_fac=0.05, a_imp=1.0, akap=KAPPA, grav=GRAV, rdgas=RDGAS, cp_air=CP_AIR, m_split=1):
@@ -133,6 +143,11 @@ class _RemapParams(C.Structure):
                                        "sphum"]] + [(n, C.c_double) for n in ["akap", "ptop", "rdgas", "grav", "cv_air",
                                                                               "r_vir", "cp", "t_min"]] + [
         ("fill", C.c_int)]
+
+
+class _NegAdjParams(C.Structure):
+    _fields_ = [("hydrostatic", C.c_int)] + [(n, C.c_double) for n in ["rdgas", "rvgas", "grav", "cp_air", "cp_vapor", "hlv", "hlf",
+                                                                        "c_liq", "c_ice"]]
 
 
 class _MoistParams(C.Structure):
@@ -635,6 +650,22 @@ class Context:
         """fv_fill.F90:238-256"""
         qp = C.cast(_vp(q.ptr + 8 * q_offset), _dp)
         self.lib.check(self.lib.dll.fv3_fill2d_apply(self.h, C.c_int(nk), qt.p, delp.p, qp), "fv3_fill2d_apply")
+
+    def neg_adj3(self, hydrostatic, peln, delz, delp, pt, q, species=(1, 2, 3, 4, 5, 6), qa=0, consts=None):
+        """neg_adj3 (fv_sg.F90:968-1335; fv_dynamics.F90:722-745) in place on pt (= T) and the tracer array q (A x npz x nq).
+        species: the 1-based tracer indices of sphum, liq_wat, rainwat, ice_wat, snowwat, graupel; qa: that of cld_amt, 0 = absent;
+        consts: overrides of NEG_ADJ_CONSTS"""
+        pr = _NegAdjParams()
+        pr.hydrostatic = int(bool(hydrostatic))
+        for k, val in {**NEG_ADJ_CONSTS, **(consts or {})}.items():
+            setattr(pr, k, val)
+        n3 = int(np.prod(q.shape[:3]))
+        nq = q.shape[3] if len(q.shape) > 3 else 1
+        if any(not 1 <= int(s) <= nq for s in species) or len(set(species)) != 6 or not 0 <= int(qa) <= nq:
+            raise Fv3Error(f"neg_adj3: species {tuple(species)} / cld_amt {qa} are not six distinct tracers of 1..{nq}")
+        sp = [C.cast(_vp(q.ptr + 8 * n3 * (int(s) - 1)), _dp) for s in species]
+        qap = C.cast(_vp(q.ptr + 8 * n3 * (int(qa) - 1)), _dp) if qa else None
+        self.lib.check(self.lib.dll.fv3_neg_adj3(self.h, C.byref(pr), _pp(peln), _pp(delz), delp.p, pt.p, *sp, qap), "fv3_neg_adj3")
 
     def omga_update(self, rdt, ptop, pe, delp_before, omga):
         """dyn_core.F90:1182-1191: omga = (pe - pem)*rdt on the last substep (local part, see the header)"""

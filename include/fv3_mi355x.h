@@ -618,6 +618,23 @@ int fv3_flux_accum(fv3_ctx *ctx, double *mfx, double *mfy, const double *fx, con
 int fv3_fill2d_mass(fv3_ctx *ctx, int nk, const double *q, const double *delp, double *qt);
 int fv3_fill2d_apply(fv3_ctx *ctx, int nk, const double *qt, const double *delp, double *q);
 
+/* neg_adj3 -- model/fv_sg.F90:968-1335 with its fillq (:1337-1370), call site fv_dynamics.F90:722-745 (every run with nwat == 6,
+ * after the k_split loop and before consv_am): negative qv, ql, qr, qi, qs, qg are repaired by borrowing between the phases with the
+ * temperature adjusted to conserve energy (:1055-1151), qg and qr are filled vertically (fillq, :1208-1234), qv borrows down and up
+ * the column (:1239-1286) and qa is repaired (:1289-1321).  The module parameters of fv_sg.F90:43-70 (tice, hlv0, hlf0, cv_vap, dc_ice,
+ * Li0) and d0_vap / lv00 of :1004-1014 are formed from the caller's constants_mod / gfdl_mp values below; the form without ENG_CNV_OLD.
+ * sat_adj is a local .false. (:982): the saturation block :1157-1187 is dead and not built, and with it p2, the only use of peln and
+ * delz -- the one the mode needs must still be given.
+ * pt (= T), delp, qv .. qg, qa: A x npz with halos, the species = &q(isd,jsd,1,iq) of the tracer array (qa may be NULL: no cld_amt);
+ * delz: CC x npz (NULL when hydrostatic); peln: (is:ie, npz+1, js:je) (hydrostatic only).  In place, compute domain only; npz >= 2.
+ * A cell the routine leaves unchanged keeps its bits (-0.0 aside): a state without negative water is a no-op and is not written. */
+typedef struct fv3_neg_adj_params {
+  int hydrostatic;
+  double rdgas, rvgas, grav, cp_air, cp_vapor, hlv, hlf, c_liq, c_ice;  /* the caller's constants_mod / gfdl_mp values */
+} fv3_neg_adj_params;
+int fv3_neg_adj3(fv3_ctx *ctx, const fv3_neg_adj_params *p, const double *peln, const double *delz, const double *delp,
+                 double *pt, double *qv, double *ql, double *qr, double *qi, double *qs, double *qg, double *qa);
+
 /* Per-kernel timing with HIP events recorded on the context's stream around every kernel the
  * library launches (this is what bench.py's roofline figures are measured with).  report: one line
  * "label count total_ms" per kernel label since the last report; synchronises the stream. */
