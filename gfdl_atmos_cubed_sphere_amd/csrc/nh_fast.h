@@ -795,7 +795,10 @@ struct RiemFast {
   FV3_D void w_columns(double *A, double *D, double *R, int wave, int tid) const {
 #ifdef FV3_HOST_EMU
     (void)wave; (void)tid;
-    for (int col = 0; col < kFC; col++) w_column(A + col * kFP, D + col * kFP, R + col * kFP);
+    for (int col = 0; col < kFC; col++) {   // the sweep the library ships (opt & 2) unless the option says otherwise, as on the device
+      if (opt & 2) w_column2(A + col * kFP, D + col * kFP, R + col * kFP);
+      else w_column(A + col * kFP, D + col * kFP, R + col * kFP);
+    }
 #else
     if ((tid >> 6) == wave && (tid & 63) < kFC) {
       const int col = tid & 63;

@@ -467,8 +467,11 @@ FV3_HD ProfCfg profile_col_ppm(const ColScr &c, int km, int iv, int kord, const 
 // (|kord| = 11 tests the monotonicity of the NEXT-higher cell's interface values, which a descending sweep has not
 // produced yet; it keeps the unfused sweeps below.)
 template <class Src>
-FV3_HD ProfCfg profile_col(const ColScr &c, int km, bool is_scalar, double qs, int iv, int kord, double qmin, const Src &src) {
-  if (kord_is_ppm(kord)) return profile_col_ppm(c, km, iv, kord, src);   // "if (kord > 7) ... else call ppm_profile"
+FV3_HD ProfCfg profile_col(const ColScr &c, int km, bool is_scalar, double qs, int iv, int kord, double qmin, const Src &src,
+                           bool ppm_below_8 = true) {
+  // "if (kord > 7) ... else call ppm_profile" (map_scalar :87, map1_ppm :182, map1_q2 :395).  mapn_tracer (ppm_below_8 = false) has
+  // no such test: it calls scalar_profile for every kord (:273), where abs(kord) <= 8 is one case of Huynh's constraint (:753-755)
+  if (ppm_below_8 && kord_is_ppm(kord)) return profile_col_ppm(c, km, iv, kord, src);
   const int ak = kord < 0 ? -kord : kord;
   ProfCfg pc{km, iv, ak, is_scalar, qmin, ak != 11 && ak != 12};
 #define DP(k) (CS(pe1, (k) + 1) - CS(pe1, k))
@@ -1345,7 +1348,9 @@ struct RemapFields {
         bool side_by_side = nl > 1;
         for (int n = 0; n < nl; n++) {
           const int a = kord_tr[iq0 + n] < 0 ? -kord_tr[iq0 + n] : kord_tr[iq0 + n];
-          if (a == 11 || a == 12 || kord_is_ppm(kord_tr[iq0 + n])) side_by_side = false;  // these keep a2, a3, a4 in slabs
+          // |kord| 11, 12 and ppm_profile keep a2, a3, a4 in slabs.  With nq > 5 (mapn_tracer) a kord <= 7 is scalar_profile too and
+          // would fit the side-by-side form; it is a non-default setting and stays on the one-tracer path below
+          if (a == 11 || a == 12 || kord_is_ppm(kord_tr[iq0 + n])) side_by_side = false;
         }
         if (side_by_side) {
           ColScr cg = c;
@@ -1374,7 +1379,8 @@ struct RemapFields {
           const int iq = iq0 + n;
           double *qq = q + (size_t)iq * nA * km;
           if (!side_by_side) {
-            const ProfCfg pc = profile_col(c, km, true, 0., 0, kord_tr[iq], 0., [&](int k) { return qq[(size_t)(k - 1) * nA + fo]; });
+            const ProfCfg pc = profile_col(c, km, true, 0., 0, kord_tr[iq], 0., [&](int k) { return qq[(size_t)(k - 1) * nA + fo]; },
+                                           !(p.nq > 5));   // nq > 5: mapn_tracer, scalar_profile whatever the kord (fv_mapz.F90:380-397)
             map_col(c, km, p.nq > 5, pc, [&](int k, double v_) { qq[(size_t)(k - 1) * nA + fo] = v_; });
           }
           if (p.fill)  // fv_operators.F90:337 / fv_mapz.F90:390

@@ -18,14 +18,17 @@
  *               check_golden_ppm_through_fv_tp_2d; -m gpu and host-emulation tests, x and y sweeps, hord 5, -5, 6, 8).
  *               set_eta (L79, L127; restated in the package's test_cases.py) against the reference's own stand-alone
  *               fv_eta.F90 compiled here (oracle/Makefile target `ref` -> oracle/_ref/, tests/golden/set_eta_golden.npz).
- *   unpinned  : everything else (fv_tp_2d, c_sw, d_sw, column solvers, remap incl. ppm_profile, compute_total_energy and the
- *               energy fixer, Rayleigh_Super / _Friction, adv_pe, cubed_to_latlon).  The reference
- *               ships no unit tests / golden vectors, and its Fortran
- *               cannot be built here without writing stand-ins for the absent FMS library,
- *               which the build rules forbid.  Those operators are pinned only by the
- *               reference's conservation identities and other size-independent properties (tests/test_oracle_properties.py:
- *               column integrals / constants / linear profiles under every remap profile family; tests/parity_*.py: global
- *               mass on the six faces, energy closure of the fixer, the O(h^2) closure of adv_pe's uniform-pressure term).
+ *               fv_tp_2d (every hord, mass fluxes, damping, lim_fac), copy_corners, c_sw, d_sw, a2b_ord4, update_dz_c / _d,
+ *               Riem_Solver_c / Riem_Solver3 (SIM1), map_scalar / map1_ppm / map1_q2 / mapn_tracer and fillz against the
+ *               reference's OWN COMPILED FORTRAN: oracle/Makefile target `ref` compiles its model .F90 files unmodified against the
+ *               stand-ins of oracle/ref/fms_standins.F90 -> oracle/_ref/libfv3ref.so (tests/ref_lib.py, tests/test_reference_pin.py,
+ *               tests/golden/refpin_*.npz).  Bit-identical except the Riemann solvers (libm vs include/fv3_math.h; bounds in
+ *               tests/refpin_common.py).
+ *   unpinned  : Lagrangian_to_Eulerian as a whole, tracer_2d, compute_total_energy and the energy fixer, Rayleigh_Super /
+ *               _Friction, adv_pe, cubed_to_latlon, the pressure-gradient family, SIM3 / SIM3p0 / RIM_2D; a2b_ord4 at a cube
+ *               corner and d_sw with nord > 0 on a tile that owns one (the stand-ins for great_circle_dist and fill_corners
+ *               stop).  Those are pinned only by the reference's conservation identities and other size-independent properties
+ *               (tests/test_oracle_properties.py, tests/parity_*.py).
  *
  * Scope of the restated branches: grid_type 4 (doubly periodic) and grid_type < 3 (the cubed sphere, one whole tile per
  * face: the edge / corner branches of c_sw, d_sw, fv_tp_2d, xppm / yppm, xtp_u / ytp_v, a2b_ord4, update_dz_c / _d), with

@@ -231,12 +231,16 @@ static int ppm_profile_column(double *a4, const double *delp, int km, int iv, in
 
 /* scalar_profile (is_scalar=1, :546-916) / cs_profile (is_scalar=0, :919-1300) for one column.
  * delp[1..km], a4 as above (A4(1,k) on entry). Returns 0 or FVO_ERR_UNSUPPORTED. */
-int fvo_profile_column(int is_scalar, double qs, double *a4, const double *delp, int km, int iv, int kord, double qmin) {
+/* ppm_below_8: the caller is one of the map routines that test "if (kord > 7) ... else ppm_profile" on the SIGNED kord (map_scalar
+ * :87, map1_ppm :182, map1_q2 :395).  mapn_tracer has no such test: it calls scalar_profile for every kord (:273), where
+ * abs(kord) <= 8 is one case of Huynh's constraint (select case (abs(kord)), case (0:8), :753-755). */
+static int profile_column(int is_scalar, double qs, double *a4, const double *delp, int km, int iv, int kord, double qmin,
+                          int ppm_below_8) {
   int k;
   const int ak = abs(kord);
   if (!(iv == -2 || iv == -1 || iv == 0 || iv == 1)) return FVO_ERR_UNSUPPORTED;
-  if (kord <= 7) return ppm_profile_column(a4, delp, km, iv, kord); /* "if (kord > 7) ... else ppm_profile", the SIGNED kord */
-  if (!(ak >= 8 && ak <= 15)) return FVO_ERR_UNSUPPORTED;
+  if (ppm_below_8 && kord <= 7) return ppm_profile_column(a4, delp, km, iv, kord);
+  if (!(ak <= 15 && (ak >= 8 || !ppm_below_8))) return FVO_ERR_UNSUPPORTED;
   double *gam = dalloc(km + 3), *q = dalloc(km + 3);
   unsigned char *extm = (unsigned char *)calloc(km + 3, 1), *ext5 = (unsigned char *)calloc(km + 3, 1),
                 *ext6 = (unsigned char *)calloc(km + 3, 1);
@@ -460,6 +464,10 @@ static void map_column(int km, int kn, const double *pe1, const double *pe2, con
   }
 }
 
+int fvo_profile_column(int is_scalar, double qs, double *a4, const double *delp, int km, int iv, int kord, double qmin) {
+  return profile_column(is_scalar, qs, a4, delp, km, iv, kord, qmin, 1);
+}
+
 /* Remap one column: which = 0 map_scalar (scalar_profile), 1 map1_ppm (cs_profile), 2 map1_q2 (scalar_profile,
  * /dp2), 3 mapn_tracer arithmetic.  q1[1..km] in, q2[1..kn] out (may alias q1: a4(1,:) is a copy). */
 int fvo_remap_column(int which, int km, const double *pe1, const double *pe2, const double *q1, double *q2, double qs,
@@ -471,7 +479,7 @@ int fvo_remap_column(int which, int km, const double *pe1, const double *pe2, co
     dp2[k] = pe2[k + 1] - pe2[k];
     A4(1, k) = q1[k];
   }
-  rc = fvo_profile_column(which != 1, qs, a4, dp1, km, iv, kord, qmin);
+  rc = profile_column(which != 1, qs, a4, dp1, km, iv, kord, qmin, which != 3);
   if (!rc) map_column(km, km, pe1, pe2, dp1, a4, q2, which >= 2 ? dp2 : NULL, which == 3);
   free(a4); free(dp1); free(dp2);
   return rc;

@@ -1,0 +1,4 @@
+! Stand-in for the FMS header of the same name (test infrastructure, see fms_standins.F90): the two macros the
+! reference's fv_arrays.F90 expands.
+#define _ALLOCATABLE allocatable
+#define _NULL

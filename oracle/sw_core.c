@@ -618,7 +618,7 @@ static void tp_wind_line_cs(const double *w, const double *dx, const double *rdx
       }
     }
     for (i = is - 1; i <= ie + 1; i++) b0[i] = bl[i] + br[i];
-    if (iord == 1 || iord == 4 || iord >= 5) {
+    if (iord != 2 && iord != 3) { /* 1, 4 and the reference's "else" (:2337): 5, 6, 7 and every iord <= 0 */
       if (iord == 1) {
         for (i = is - 1; i <= ie + 1; i++) smt5[i] = fabs(lim_fac * b0[i]) < fabs(bl[i] - br[i]);
       } else if (iord == 4) {

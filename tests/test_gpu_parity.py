@@ -336,7 +336,9 @@ def test_remap(prod, hydrostatic, last_step, kord_tm, kord, nq):
 def test_remap_ppm_profile(prod, hydrostatic, last_step, kord_tm, kord, nq):
     """kord <= 7: the map routines take ppm_profile + ppm_limiters (fv_operators.F90:1382-1723) instead of cs_profile: Huynh's
     2nd constraint (7), the positive-definite / full-monotonicity / standard limiters (6, 5, 4, 3), for winds, w, T (|kord_tm|)
-    and tracers (iv = -1, -2, 1, 0); a NEGATIVE kord_mt / kord_tr also fails the reference's "kord > 7" test and lands there"""
+    and tracers (iv = -1, -2, 1, 0); a NEGATIVE kord_mt / kord_tr also fails the reference's "kord > 7" test and lands there.
+    The tracers of the two cases with nq > 5 go through mapn_tracer, which has no such test and runs scalar_profile whatever the
+    kord (fv_operators.F90:273, case (0:8) at :753; held to the reference's compiled mapn_tracer by tests/test_reference_pin.py)."""
     R.check_remap(prod, hydrostatic=hydrostatic, last_step=last_step, kord_tm=kord_tm, kord=kord, nq=nq)
 
 

@@ -37,3 +37,5 @@ def test_package_never_imports_oracle_or_hostemu():
                 src = open(os.path.join(dp, f)).read()
                 assert "oracle_lib" not in src and "libfvo" not in src and "fvo.h" not in src, f
                 assert "libfv3_hostemu" not in src, f
+                # ... nor the reference's compiled Fortran and its binding (tests/ref_lib.py, oracle/_ref/libfv3ref.so)
+                assert "ref_lib" not in src and "libfv3ref" not in src and "refpin" not in src, f
