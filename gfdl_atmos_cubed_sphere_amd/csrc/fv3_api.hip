@@ -171,6 +171,13 @@ struct fv3_ctx {
   std::vector<ProfRec> prof;
   struct fv3_group *grp = nullptr;   // the faces one rank holds, launched together (fv3_group_create)
   int grp_idx = 0;
+  // FV3_MI355X_POISON (debug switch, default off): every double work array of the library is allocated through work_alloc, which
+  // then registers it here -- guard bands around it, the poison pattern in it at every compute entry (poison_entry)
+  int poison = 0;
+  int entry_depth = 0;               // a compute entry that calls another one poisons once
+  const char *last_entry = "";       // the compute entry that ran before this one (carried-slots table)
+  struct WorkArr { const char *group; int idx; double **slot; double *base; size_t n; bool refill; };
+  std::vector<WorkArr> work;
 };
 
 static thread_local std::string g_err;
@@ -452,6 +459,123 @@ static int launch_w(fv3_ctx *c, const char *label, int nwaves, const F &f) {
   return rc;
 }
 
+
+// ---- FV3_MI355X_POISON: the memory contract of the work arrays (debug switch; docs/SWITCHES.md) -----------------------------------
+// The work arrays (cs_scr, scratch, mflux, ke_scr, heat_scr, remap_scr, the message buffers) are allocated once and shared between
+// routines, so a kernel that reads one before it has written it sees zeros in a fresh context and another routine's leftovers in a
+// model run.  Under the switch every such array lies between two guard bands of kPoisonGuard doubles, holds the poison pattern when it
+// is allocated and again at the head of every compute entry, and the guard bands are checked by fv3_sync and fv3_destroy.  The
+// pattern is finite, sign-alternating and not constant (a stencil difference does not cancel it; min / max do not drop it, which they
+// would a NaN under -fno-honor-nans).  Integer tables and the coefficient tables the host uploads whole never go through here: a
+// poisoned index would send a kernel out of bounds.  LDS: poisoned by the host emulation's launcher only -- on the GPU it cannot be.
+constexpr size_t kPoisonGuard = 1024;   // doubles on either side (8 KB: the array keeps the allocator's alignment)
+FV3_HD double poison_value(size_t i) { return ((i & 1) ? -1.0e30 : 1.0e30) * (double)(1 + (int)(i % 7)); }
+struct PoisonFill {
+  double *p;
+  size_t n;
+  static constexpr int CH = 4096;
+  FV3_HD void operator()(int bx, int, int, int tid, double *) const {
+    for (size_t idx = (size_t)bx * CH + tid; idx < (size_t)(bx + 1) * CH && idx < n; idx += kNT) p[idx] = poison_value(idx);
+  }
+};
+static int poison_fill(fv3_ctx *c, double *p, size_t n) {
+  if (!n) return 0;
+  Dim3 grid;
+  grid.x = (unsigned)((n + PoisonFill::CH - 1) / PoisonFill::CH);
+  grid.y = 1;
+  grid.z = 1;
+  return launch_p(c, "poison_fill", grid, 0, PoisonFill{p, n});
+}
+// The carried slots: what a compute entry takes over from the entry that ran before it on this context, and therefore is not
+// poisoned at its head.  Each row is a statement of the contract (include/fv3_mi355x.h says at the entries concerned which calls may
+// not come in between): `entry` reads slots lo .. hi of `group` as `from` left them.
+// TODAY THE TABLE HAS NO ROW: every work array is written by the call that reads it.  What the sequences hand from one entry to the
+// next travels in the caller's arrays (crx .. yfx and the fluxes from fv3_d_sw to fv3_d_sw_inline_q and to fv3_tracer_2d_*; what
+// fv3_d_sw_interior stores for fv3_d_sw_rest; heat_s for fv3_heat_source_accum; u2f for fv3_rayleigh_apply) or in the integer /
+// coefficient tables the host uploads (ksplt of fv3_tracer_2d_step, it > 1), which are not work arrays.  tests/test_memory_contract_*
+// hold that: the sub-step loops, the split d_sw and the tracer sub-cycle run with every work array poisoned between any two entries.
+// A kernel that is made to leave something in a work array for a later entry adds its row here, and the sentence to the header.
+// Entries that only move data (halo exchanges, copies, uploads, reductions of caller arrays) are not compute entries: they neither
+// poison nor count as "the entry before".
+struct CarriedSlots { const char *entry, *group; int lo, hi; const char *from; };
+static const CarriedSlots kCarried[] = {
+  {nullptr, nullptr, 0, -1, nullptr},   // end of the table
+};
+static int poison_entry(fv3_ctx *c, const char *entry) {
+  for (const fv3_ctx::WorkArr &w : c->work) {
+    if (!w.refill) continue;   // message buffers: in flight between a halo start and its complete, where compute entries may run
+    bool keep = false;
+    for (const CarriedSlots &r : kCarried)
+      if (r.entry && !std::strcmp(r.entry, entry) && !std::strcmp(r.group, w.group) && w.idx >= r.lo && w.idx <= r.hi && !std::strcmp(r.from, c->last_entry))
+        keep = true;
+    if (!keep)
+      if (int rc = poison_fill(c, *w.slot, w.n)) return fail("%s: poison fill of %s[%d] failed: %s", entry, w.group, w.idx, rt_errstr(rc));
+  }
+  c->last_entry = entry;
+  return 0;
+}
+struct EntryScope {
+  fv3_ctx *c;
+  int rc = 0;
+  EntryScope(fv3_ctx *c_, const char *entry) : c(c_) {
+    if (!c) return;
+#ifdef FV3_HOST_EMU
+    rt_lds_poison() = c->poison;
+#endif
+    if (c->entry_depth++ == 0 && c->poison) rc = poison_entry(c, entry);
+  }
+  ~EntryScope() { if (c) c->entry_depth--; }
+};
+// at the head of every extern "C" compute routine
+#define FV3_ENTRY(c)                          \
+  EntryScope entry_scope_((c), __func__);     \
+  if (entry_scope_.rc) return 1
+// every internal allocation of a double work array: n doubles into *slot.  Switch off: rt_malloc and nothing else.
+static int work_alloc(fv3_ctx *c, const char *group, int idx, double **slot, size_t n, bool refill = true) {
+  if (!c->poison) return rt_malloc((void **)slot, n * sizeof(double));
+  double *base = nullptr;
+  if (int rc = rt_malloc((void **)&base, (n + 2 * kPoisonGuard) * sizeof(double))) return rc;
+  *slot = base + kPoisonGuard;
+  c->work.push_back({group, idx, slot, base, n, refill});
+  int rc = poison_fill(c, base, kPoisonGuard);
+  if (!rc) rc = poison_fill(c, *slot, n);
+  if (!rc) rc = poison_fill(c, *slot + n, kPoisonGuard);
+  if (!rc && !refill) rc = rtf_sync(c->stream);   // (another stream writes a message buffer)
+  return rc;
+}
+static void work_free(fv3_ctx *c, double **slot) {
+  if (!*slot) return;
+  void *p = *slot;
+  for (size_t i = 0; i < c->work.size(); i++)
+    if (c->work[i].slot == slot) {
+      p = c->work[i].base;
+      c->work.erase(c->work.begin() + (long)i);
+      break;
+    }
+  rt_free(p);
+  *slot = nullptr;
+}
+// the guard bands of every work array against the pattern; the first damaged one is reported through fail()
+static int work_check_guards(fv3_ctx *c, const char *where) {
+  if (c->work.empty()) return 0;
+  RT(rtf_sync(c->stream));
+  std::vector<double> band(2 * kPoisonGuard);
+  for (const fv3_ctx::WorkArr &w : c->work) {
+    RT(rt_d2h(band.data(), w.base, sizeof(double) * kPoisonGuard, c->stream));
+    RT(rt_d2h(band.data() + kPoisonGuard, w.base + kPoisonGuard + w.n, sizeof(double) * kPoisonGuard, c->stream));
+    RT(rt_sync(c->stream));
+    for (size_t i = 0; i < 2 * kPoisonGuard; i++) {
+      const double want = poison_value(i % kPoisonGuard);
+      if (std::memcmp(&band[i], &want, sizeof want)) {
+        const long off = i < kPoisonGuard ? (long)i - (long)kPoisonGuard : (long)(w.n + (i - kPoisonGuard));
+        return fail("%s: guard band of work array %s[%d] (%zu doubles) damaged, first at offset %ld (found %.17g)", where, w.group, w.idx,
+                    w.n, off, band[i]);
+      }
+    }
+  }
+  return 0;
+}
+
 extern "C" int fv3_profile(fv3_ctx *c, int enable) {
   if (!c) return fail("fv3_profile: null ctx");
   c->prof_on = enable != 0;
@@ -550,6 +674,8 @@ extern "C" int fv3_create(const fv3_domain *dom, fv3_ctx **out) {
     c->use_march = e ? std::atoi(e) : 1;
     e = std::getenv("FV3_MI355X_SIDE_STREAM");
     c->use_side = e ? std::atoi(e) : 1;
+    e = std::getenv("FV3_MI355X_POISON");
+    c->poison = (e && std::atoi(e) != 0) ? 1 : 0;
     e = std::getenv("FV3_MI355X_SPONGE_MARCH");
     c->sponge_march = e ? std::atoi(e) : 1;
     c->round_simds = 0;
@@ -653,6 +779,7 @@ extern "C" int fv3_destroy(fv3_ctx *c) {
     g->n = 0;
     c->grp = nullptr;
   }
+  const int guards = c->poison ? work_check_guards(c, "fv3_destroy") : 0;   // (reported after everything is freed)
   cube_plans_free(c);
   fv3_comm_destroy(c);
   if (c->dev_metrics) rt_free(c->dev_metrics);
@@ -660,20 +787,20 @@ extern "C" int fv3_destroy(fv3_ctx *c) {
   if (c->lev_d) rt_free(c->lev_d);
   if (c->dp0) rt_free(c->dp0);
   if (c->akbk) rt_free(c->akbk);
-  if (c->remap_scr) rt_free(c->remap_scr);
+  work_free(c, &c->remap_scr);
   if (c->ray_d) rt_free(c->ray_d);
   if (c->rff_d) rt_free(c->rff_d);
   delete c->reg;
-  if (c->trc_d) rt_free(c->trc_d);
+  work_free(c, &c->trc_d);
   if (c->trc_i) rt_free(c->trc_i);
   if (c->ones_i) rt_free(c->ones_i);
   if (c->kord_tr_dev) rt_free(c->kord_tr_dev);
   if (c->edge_dev) rt_free(c->edge_dev);
   if (c->lev_ext_d) rt_free(c->lev_ext_d);
   if (c->lev_ext_i) rt_free(c->lev_ext_i);
-  for (auto &s : c->scratch) if (s) rt_free(s);
-  for (auto &s : c->mflux) if (s) rt_free(s);
-  for (auto &s : c->cs_scr) if (s) rt_free(s);
+  for (auto &s : c->scratch) work_free(c, &s);
+  for (auto &s : c->mflux) work_free(c, &s);
+  for (auto &s : c->cs_scr) work_free(c, &s);
   if (c->cg_dev) rt_free(c->cg_dev);
   if (c->stream2) rt_stream_destroy(c->stream2);
   if (c->ev_fork) rt_event_destroy(c->ev_fork);
@@ -684,10 +811,10 @@ extern "C" int fv3_destroy(fv3_ctx *c) {
     if (ls.klist_m) rt_free(ls.klist_m);
   }
   if (c->klist_z) rt_free(c->klist_z);
-  if (c->ke_scr) rt_free(c->ke_scr);
-  for (double *h : c->heat_scr) if (h) rt_free(h);
+  work_free(c, &c->ke_scr);
+  for (auto &h : c->heat_scr) work_free(c, &h);
   delete c;
-  return 0;
+  return guards;
 }
 
 extern "C" int fv3_set_stream(fv3_ctx *c, void *stream) {
@@ -890,6 +1017,7 @@ extern "C" int fv3_memset(fv3_ctx *c, void *dst, int value, size_t bytes) {
 }
 extern "C" int fv3_sync(fv3_ctx *c) {
   RT(rtf_sync(c ? c->stream : nullptr));
+  if (c && c->poison) return work_check_guards(c, "fv3_sync");
   return 0;
 }
 
@@ -1178,7 +1306,7 @@ static int launch_pass(fv3_ctx *c, const char *label, int i0, int i1, int j0, in
 // n-th work array of the cubed-sphere kernels: (nid+1) x (njd+1) x (npz+1) doubles, allocated on first use
 static double *cs_scratch(fv3_ctx *c, int n) {
   if (!c->cs_scr[n]) {
-    if (rt_malloc((void **)&c->cs_scr[n], sizeof(double) * c->g.nB() * (size_t)(c->g.npz + 1))) return nullptr;
+    if (work_alloc(c, "cs_scr", n, &c->cs_scr[n], c->g.nB() * (size_t)(c->g.npz + 1))) return nullptr;
   }
   return c->cs_scr[n];
 }
@@ -1379,6 +1507,7 @@ extern "C" int fv3_fv_tp_2d(fv3_ctx *c, int nk, const double *q, const double *c
                             double *fx, double *fy, const double *xfx, const double *yfx, const double *ra_x,
                             const double *ra_y, const double *mfx, const double *mfy, const double *mass, int nord,
                             double damp_c) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_fv_tp_2d: context has no grid (call fv3_grid_upload)");
   if (!tp_ord_supported(hord)) return fail("fv3_fv_tp_2d: hord=%d not supported -- " FV3_HORD_TABLE, hord);
   if (nord > 2) return fail("fv3_fv_tp_2d: nord=%d > 2", nord);
@@ -1440,6 +1569,7 @@ struct PpmLineTile {
 };
 
 extern "C" int fv3_ppm_line(fv3_ctx *c, int iord, int which, const double *h, const double *cr, double *flux, int n) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_ppm_line: context has no grid");
   if (!h || !cr || !flux || n < 1) return fail("fv3_ppm_line: bad arguments");
   if (which == 0) {
@@ -1510,6 +1640,7 @@ extern "C" int fv3_c_sw(fv3_ctx *c, double *delpc, const double *delp, double *p
                         const double *u, const double *v, const double *w, double *uc, double *vc, double *ua,
                         double *va, double *wc, double *ut, double *vt, double *divg_d, int nord, double dt2,
                         int hydrostatic, int dord4) {
+  FV3_ENTRY(c);
   (void)dord4;  // ua, va are produced on is-1:ie+1 (what c_sw/d_sw read); see header
   if (!c || !c->grid_ready) return fail("fv3_c_sw: context has no grid (call fv3_grid_upload)");
   if (!hydrostatic && (!w || !wc)) return fail("fv3_c_sw: nonhydrostatic call needs w and wc");
@@ -1601,8 +1732,8 @@ static int dispatch_hord_all(int hord, Fn &&fn) {
 
 static int ensure_mflux(fv3_ctx *c) {
   const Grid &g = c->g;
-  if (!c->mflux[0]) RT(rt_malloc((void **)&c->mflux[0], sizeof(double) * g.nFX() * g.npz));
-  if (!c->mflux[1]) RT(rt_malloc((void **)&c->mflux[1], sizeof(double) * g.nFY() * g.npz));
+  if (!c->mflux[0]) RT(work_alloc(c, "mflux", 0, &c->mflux[0], g.nFX() * g.npz));
+  if (!c->mflux[1]) RT(work_alloc(c, "mflux", 1, &c->mflux[1], g.nFY() * g.npz));
   return 0;
 }
 
@@ -1693,7 +1824,7 @@ static int dsw_transport_march(fv3_ctx *c, const DswArgs &a, int region = 0) {
 static int dsw_momentum_march(fv3_ctx *c, const DswArgs &a, int part = 0) {
   const Grid &g = c->g;
   const bool fused_m = dsw_momentum_fused(c, a);
-  if (!fused_m && !c->ke_scr) RT(rt_malloc((void **)&c->ke_scr, sizeof(double) * g.nB() * g.npz));
+  if (!fused_m && !c->ke_scr) RT(work_alloc(c, "ke_scr", 0, &c->ke_scr, g.nB() * g.npz));
   if (fused_m) {
     MarchDims mf = make_march_dims(g, seg_rows(c, (a.mask_w && !c->tj_env_fused) ? 55 : c->march_tj_mom, g.npz));
     mf.klist = c->klist_m;
@@ -2179,7 +2310,7 @@ static int d_sw_impl(fv3_ctx *c, const fv3_dsw_params *p, double *delpc, const d
     if (phase == 1) return 0;  // no interior / rest split on a face: everything runs in 'rest' (or the unsplit call)
     if (!a.heat_s || !a.diss_e) {
       for (int n = 0; n < 2; n++)
-        if (!c->heat_scr[n]) RT(rt_malloc((void **)&c->heat_scr[n], sizeof(double) * g.nCC() * npz));
+        if (!c->heat_scr[n]) RT(work_alloc(c, "heat_scr", n, &c->heat_scr[n], g.nCC() * npz));
       a.skip_heat = (!a.heat_s && !a.diss_e) ? 1 : 0;   // the marching kernel of the face interior then stores neither
       if (!a.heat_s) a.heat_s = c->heat_scr[0];
       if (!a.diss_e) a.diss_e = c->heat_scr[1];
@@ -2203,7 +2334,7 @@ static int d_sw_impl(fv3_ctx *c, const fv3_dsw_params *p, double *delpc, const d
   const bool all_bf = FV3_BF && fused && fused_m && march_m && c->n_damp == 0 && c->n_rest_m == 0;
   if ((!a.heat_s || !a.diss_e) && !all_bf) {
     for (int n = 0; n < 2; n++)
-      if (!c->heat_scr[n]) RT(rt_malloc((void **)&c->heat_scr[n], sizeof(double) * g.nCC() * npz));
+      if (!c->heat_scr[n]) RT(work_alloc(c, "heat_scr", n, &c->heat_scr[n], g.nCC() * npz));
     if (!a.heat_s) a.heat_s = c->heat_scr[0];
     if (!a.diss_e) a.diss_e = c->heat_scr[1];
   }
@@ -2284,9 +2415,9 @@ static int d_sw_impl(fv3_ctx *c, const fv3_dsw_params *p, double *delpc, const d
       const double *divg_d, double *mfx, double *mfy, double *cx, double *cy, double *crx, double *cry, double *xfx,   \
       double *yfx, const double *q_con, double *delp_out, double *pt_out, double *u_out, double *v_out, double *w_out, \
       double *q_con_out, double *heat_s, double *diss_e
-extern "C" int fv3_d_sw(FV3_DSW_PARAMS) { return d_sw_impl(FV3_DSW_ARGS, 0); }
-extern "C" int fv3_d_sw_interior(FV3_DSW_PARAMS) { return d_sw_impl(FV3_DSW_ARGS, 1); }
-extern "C" int fv3_d_sw_rest(FV3_DSW_PARAMS) { return d_sw_impl(FV3_DSW_ARGS, 2); }
+extern "C" int fv3_d_sw(FV3_DSW_PARAMS) { FV3_ENTRY(c); return d_sw_impl(FV3_DSW_ARGS, 0); }
+extern "C" int fv3_d_sw_interior(FV3_DSW_PARAMS) { FV3_ENTRY(c); return d_sw_impl(FV3_DSW_ARGS, 1); }
+extern "C" int fv3_d_sw_rest(FV3_DSW_PARAMS) { FV3_ENTRY(c); return d_sw_impl(FV3_DSW_ARGS, 2); }
 
 // ---- periodic halo fill (single rank owns the whole doubly periodic tile) ------------------------
 struct HaloPeriodic {
@@ -2644,9 +2775,8 @@ extern "C" int fv3_comm_destroy(fv3_ctx *c) {
 #endif
   c->comm = nullptr;
   for (int d = 0; d < 8; d++) {
-    if (c->msg_send[d]) rt_free(c->msg_send[d]);
-    if (c->msg_recv[d]) rt_free(c->msg_recv[d]);
-    c->msg_send[d] = c->msg_recv[d] = nullptr;
+    work_free(c, &c->msg_send[d]);
+    work_free(c, &c->msg_recv[d]);
     c->msg_cap[d] = 0;
   }
   if (c->ev_packed) rt_event_destroy(c->ev_packed);
@@ -2672,10 +2802,10 @@ extern "C" int fv3_halo_start(fv3_ctx *c, int nfields, const fv3_halo_field *fie
   if (fv3_halo_message_elems(c, nfields, fields, elems)) return 1;
   for (int d = 0; d < 8; d++) {
     if (elems[d] > c->msg_cap[d]) {
-      if (c->msg_send[d]) rt_free(c->msg_send[d]);
-      if (c->msg_recv[d]) rt_free(c->msg_recv[d]);
-      RT(rt_malloc((void **)&c->msg_send[d], sizeof(double) * elems[d]));
-      RT(rt_malloc((void **)&c->msg_recv[d], sizeof(double) * elems[d]));
+      work_free(c, &c->msg_send[d]);
+      work_free(c, &c->msg_recv[d]);
+      RT(work_alloc(c, "msg_send", d, &c->msg_send[d], elems[d], false));
+      RT(work_alloc(c, "msg_recv", d, &c->msg_recv[d], elems[d], false));
       c->msg_cap[d] = elems[d];
     }
   }
@@ -2737,9 +2867,8 @@ static void cube_plans_free(fv3_ctx *c) {
     delete p;
     c->cube_plan[n] = nullptr;
   }
-  if (c->cube_send) rt_free(c->cube_send);
-  if (c->cube_recv) rt_free(c->cube_recv);
-  c->cube_send = c->cube_recv = nullptr;
+  work_free(c, &c->cube_send);
+  work_free(c, &c->cube_recv);
   c->cube_cap_send = c->cube_cap_recv = 0;
 }
 extern "C" long fv3_cube_table(int npx, int ng, int kind, int member, int face, long *dst, int *src_face, int *comp, long *src, int *sign) {
@@ -2897,13 +3026,13 @@ extern "C" int fv3_cube_halo_start(int nctx, fv3_ctx *const *ctxs, const int *fa
       }
     }
     if (so > c->cube_cap_send) {
-      if (c->cube_send) rt_free(c->cube_send);
-      RT(rt_malloc((void **)&c->cube_send, sizeof(double) * so));
+      work_free(c, &c->cube_send);
+      RT(work_alloc(c, "cube_send", 0, &c->cube_send, so, false));
       c->cube_cap_send = so;
     }
     if (ro > c->cube_cap_recv) {
-      if (c->cube_recv) rt_free(c->cube_recv);
-      RT(rt_malloc((void **)&c->cube_recv, sizeof(double) * ro));
+      work_free(c, &c->cube_recv);
+      RT(work_alloc(c, "cube_recv", 0, &c->cube_recv, ro, false));
       c->cube_cap_recv = ro;
     }
     for (int f = 0; f < nfields; f++) {
@@ -3208,7 +3337,7 @@ static int need_scratch(fv3_ctx *c, int n) {
   const size_t nblk = (((size_t)(c->g.nx + 2) * (c->g.ny + 2) + 63) / 64) * 64;
   const size_t bytes = (c->g.nA() > nblk ? c->g.nA() : nblk) * (size_t)(c->g.npz + 1) * sizeof(double);
   for (int s = 0; s < n; s++)
-    if (!c->scratch[s]) RT(rt_malloc((void **)&c->scratch[s], bytes));
+    if (!c->scratch[s]) RT(work_alloc(c, "scratch", s, &c->scratch[s], bytes / sizeof(double)));
   return 0;
 }
 
@@ -3263,6 +3392,7 @@ extern "C" int fv3_set_dp_ref(fv3_ctx *c, const double *dp0) {
 
 extern "C" int fv3_update_dz_c(fv3_ctx *c, double dt, const double *zs, const double *ut, const double *vt,
                                const double *gz_in, double *gz, double *ws) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_update_dz_c: context has no grid");
   if (!c->dp0_ready) return fail("fv3_update_dz_c: call fv3_set_dp_ref first");
   if (gz_in == gz) return fail("fv3_update_dz_c: gz_in and gz must not alias");
@@ -3316,6 +3446,7 @@ extern "C" int fv3_set_ray_fast(fv3_ctx *c, int kmax, int k_rf, double dm, const
 }
 
 extern "C" int fv3_ray_fast(fv3_ctx *c, double *u, double *v, double *w, int hydrostatic) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_ray_fast: context has no grid");
   if (c->rayf_kmax < 0) return fail("fv3_ray_fast: call fv3_set_ray_fast first");
   if (!u || !v || (!hydrostatic && !w)) return fail("fv3_ray_fast: null argument");
@@ -3326,6 +3457,7 @@ extern "C" int fv3_ray_fast(fv3_ctx *c, double *u, double *v, double *w, int hyd
 }
 
 extern "C" int fv3_mix_dp(fv3_ctx *c, int hydrostatic, double *w, double *delp, double *pt) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_mix_dp: context has no grid");
   if (!c->akbk_ready) return fail("fv3_mix_dp: call fv3_set_ak_bk first (dpmin is 1 %% of the reference thickness of a layer)");
   if (!delp || !pt || (!hydrostatic && !w)) return fail("fv3_mix_dp: null argument");
@@ -3345,6 +3477,7 @@ extern "C" int fv3_set_condensate(fv3_ctx *c, const double *q_con, const double 
 
 extern "C" int fv3_riem_solver_c(fv3_ctx *c, double dt, const fv3_nh_consts *cn, const double *hs, const double *w3,
                                  const double *pt, const double *delp, double *gz, double *pef, const double *ws) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !cn) return fail("fv3_riem_solver_c: bad context/arguments");
   if (cn->a_imp <= 0.5) {      // nh_utils.F90:449-459: a_imp < -0.01 SIM3p0_solver, otherwise RIM_2D(c_core = .true.)
     if (c->q_con) return fail("fv3_riem_solver_c: use_cond with a_imp <= 0.5 (SIM3p0 / RIM_2D) is not built");
@@ -3387,6 +3520,7 @@ extern "C" int fv3_riem_solver3(fv3_ctx *c, double dt, const fv3_nh_consts *cn, 
                                 double *delz, const double *pt, const double *delp, double *zh, double *pe, double *ppe,
                                 double *pk3, double *pk, double *peln, const double *ws, int use_logp, int last_call,
                                 int fp_out) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !cn) return fail("fv3_riem_solver3: bad context/arguments");
   if (last_call && (!pe || !pk || !peln)) return fail("fv3_riem_solver3: last_call needs pe, pk, peln");
   if (cn->a_imp <= 0.5) {      // nh_core.F90:169-177: a_imp < -0.999 SIM3p0_solver, < -0.5 SIM3_solver, otherwise RIM_2D
@@ -3443,6 +3577,7 @@ extern "C" int fv3_riem_solver3(fv3_ctx *c, double dt, const fv3_nh_consts *cn, 
 extern "C" int fv3_update_dz_d(fv3_ctx *c, int hord, const double *zs, const double *zh_in, double *zh_out,
                                const double *crx, const double *cry, const double *xfx, const double *yfx, double *ws,
                                double rdt) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_update_dz_d: context has no grid");
   if (!c->dp0_ready) return fail("fv3_update_dz_d: call fv3_set_dp_ref first");
   if (!c->lev_ready) return fail("fv3_update_dz_d: call fv3_dsw_levels_upload first");
@@ -3544,6 +3679,7 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, int hord, const double *zs, const dou
 
 extern "C" int fv3_p_grad_c(fv3_ctx *c, double dt2, const double *delpc, const double *pkc, const double *gz,
                             double *uc, double *vc, int hydrostatic) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_p_grad_c: context has no grid");
   const Grid &g = c->g;
   PGradC kf{g, dt2, hydrostatic, delpc, pkc, gz, uc, vc};
@@ -3553,6 +3689,7 @@ extern "C" int fv3_p_grad_c(fv3_ctx *c, double dt2, const double *delpc, const d
 
 extern "C" int fv3_pt_to_theta_v(fv3_ctx *c, int hydrostatic, double zvir, double kappa, double rdgas, double grav,
                                  double *pt, const double *delp, const double *delz, const double *qv, double *pkz) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_pt_to_theta_v: context has no grid");
   if (!pt || !pkz || (hydrostatic <= 0 && (!delp || !delz))) return fail("fv3_pt_to_theta_v: null field");
   if (hydrostatic < -1 || hydrostatic > 1) return fail("fv3_pt_to_theta_v: hydrostatic must be 0, 1 or -1 (pkz only)");
@@ -3586,6 +3723,7 @@ extern "C" int fv3_pt_to_theta_v(fv3_ctx *c, int hydrostatic, double zvir, doubl
 }
 
 extern "C" int fv3_c2l(fv3_ctx *c, int ord, const double *u, const double *v, double *ua, double *va) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_c2l: context has no grid");
   if (!u || !v || !ua || !va) return fail("fv3_c2l: null field");
   if (ord != 2 && ord != 4) return fail("fv3_c2l: c2l_ord must be 2 or 4");
@@ -3603,6 +3741,7 @@ extern "C" int fv3_c2l(fv3_ctx *c, int ord, const double *u, const double *v, do
 
 extern "C" int fv3_rayleigh_u2f(fv3_ctx *c, int kmax, int hydrostatic, const double *u, const double *v,
                                 const double *w, double *ua, double *va, double *u2f) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_rayleigh_u2f: context has no grid");
   if (!u || !v || !ua || !va || !u2f || (!hydrostatic && !w)) return fail("fv3_rayleigh_u2f: null field");
   const Grid &g = c->g;
@@ -3622,6 +3761,7 @@ extern "C" int fv3_rayleigh_u2f(fv3_ctx *c, int kmax, int hydrostatic, const dou
 extern "C" int fv3_rayleigh_apply(fv3_ctx *c, int kmax, int conserve, int hydrostatic, double cp, double rg, double ptop,
                                   const double *pm, const double *rf, const double *u2f, double *pt, double *delz,
                                   double *u, double *v, double *w) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_rayleigh_apply: context has no grid");
   if (!pm || !rf || !u2f || !pt || !u || !v || (!hydrostatic && (!w || !delz)))
     return fail("fv3_rayleigh_apply: null argument");
@@ -3644,6 +3784,7 @@ extern "C" int fv3_rayleigh_apply(fv3_ctx *c, int kmax, int conserve, int hydros
 extern "C" int fv3_rayleigh_super(fv3_ctx *c, int kmax, int conserve, int hydrostatic, double cp, double rg, double ptop,
                                   const double *pm, const double *rf, const double *ua, const double *va, double *pt,
                                   double *u, double *v, double *w, const double *u00, const double *v00) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_rayleigh_super: context has no grid");
   if (!pm || !rf || !ua || !va || !pt || !u || !v || (!hydrostatic && !w)) return fail("fv3_rayleigh_super: null argument");
   if ((u00 == nullptr) != (v00 == nullptr)) return fail("fv3_rayleigh_super: u00 and v00 must be given together");
@@ -3665,6 +3806,7 @@ extern "C" int fv3_rayleigh_super(fv3_ctx *c, int kmax, int conserve, int hydros
 
 extern "C" int fv3_compute_aam(fv3_ctx *c, double radius, double omega, double agrav, double ptop, const double *coslat, const double *ua,
                                const double *delp, double *aam, double *m_fac, double *ps) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_compute_aam: context has no grid");
   if (!coslat || !ua || !delp || !aam || !m_fac || !ps) return fail("fv3_compute_aam: null argument");
   AamColumns kf{c->g, radius, omega, agrav, ptop, coslat, ua, delp, aam, m_fac, ps};
@@ -3673,6 +3815,7 @@ extern "C" int fv3_compute_aam(fv3_ctx *c, double radius, double omega, double a
 }
 
 extern "C" int fv3_consv_am_apply(fv3_ctx *c, double u00, const double *l2c_u, const double *l2c_v, double *u, double *v) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_consv_am_apply: context has no grid");
   if (!l2c_u || !l2c_v || !u || !v) return fail("fv3_consv_am_apply: null argument");
   const Grid &g = c->g;
@@ -3686,6 +3829,7 @@ extern "C" int fv3_consv_am_apply(fv3_ctx *c, double u00, const double *l2c_u, c
 }
 
 extern "C" int fv3_heat_source_accum(fv3_ctx *c, double *heat_source, const double *heat_s) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !heat_source || !heat_s) return fail("fv3_heat_source_accum: bad context/arguments");
   const Grid &g = c->g;
   HeatAccum kf{g, heat_source, heat_s};
@@ -3698,6 +3842,7 @@ extern "C" int fv3_heat_source_accum(fv3_ctx *c, double *heat_source, const doub
 }
 
 extern "C" int fv3_del2_cubed(fv3_ctx *c, double *q, int nk, double cd, int nmax) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !q) return fail("fv3_del2_cubed: bad context/arguments");
   if (nk < 1 || nk > c->g.npz + 1) return fail("fv3_del2_cubed: nk out of range");
   if (need_scratch(c, 1)) return 1;
@@ -3720,6 +3865,7 @@ extern "C" int fv3_del2_cubed(fv3_ctx *c, double *q, int nk, double cd, int nmax
 extern "C" int fv3_apply_heat_source(fv3_ctx *c, int n_con, int hydrostatic, double bdt, double delt_max, double cp_air,
                                      double cv_air, double rdgas, double grav, double *pt, double *heat_source,
                                      const double *delp, const double *delz, double *pkz) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_apply_heat_source: context has no grid");
   if (!pt || !heat_source || !delp || !pkz || (!hydrostatic && !delz)) return fail("fv3_apply_heat_source: null field");
   const Grid &g = c->g;
@@ -3737,6 +3883,7 @@ extern "C" int fv3_apply_heat_source(fv3_ctx *c, int n_con, int hydrostatic, dou
 }
 
 extern "C" int fv3_zh_from_delz(fv3_ctx *c, const double *zs, const double *delz, double *zh) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_zh_from_delz: context has no grid");
   ZhFromDelz kf{c->g, c->g.npz, zs, delz, zh};
   RT(launch_c(c, "zh_from_delz", col_grid(c->g.nx * c->g.ny), kf));
@@ -3797,10 +3944,12 @@ static int nh_p_grad_impl(fv3_ctx *c, double *u, double *v, const double *pp, co
                           const double *pk, double dt, double top_value, double beta, double *du, double *dv);
 extern "C" int fv3_nh_p_grad(fv3_ctx *c, double *u, double *v, const double *pp, const double *gz, double gz_scale,
                              const double *delp, const double *pk, double dt, double top_value) {
+  FV3_ENTRY(c);
   return nh_p_grad_impl(c, u, v, pp, gz, gz_scale, delp, pk, dt, top_value, 0., nullptr, nullptr);
 }
 extern "C" int fv3_split_p_grad(fv3_ctx *c, double *u, double *v, const double *pp, const double *gz, double gz_scale,
                                 const double *delp, const double *pk, double beta, double dt, double top_value, double *du, double *dv) {
+  FV3_ENTRY(c);
   if (!du || !dv) return fail("fv3_split_p_grad: du, dv (U / V x npz, zero before the first call) are required");
   return nh_p_grad_impl(c, u, v, pp, gz, gz_scale, delp, pk, dt, top_value, beta, du, dv);
 }
@@ -3851,6 +4000,7 @@ static int nh_p_grad_impl(fv3_ctx *c, double *u, double *v, const double *pp, co
 
 extern "C" int fv3_omga_update(fv3_ctx *c, double rdt, double ptop, const double *pe, const double *delp_before,
                                double *omga) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !pe || !delp_before || !omga) return fail("fv3_omga_update: bad context/arguments");
   OmgaUpdate kf{c->g, c->g.npz, rdt, ptop, pe, delp_before, omga};
   RT(launch_c(c, "omga_update", col_grid(c->g.nx * c->g.ny), kf));
@@ -3858,6 +4008,7 @@ extern "C" int fv3_omga_update(fv3_ctx *c, double rdt, double ptop, const double
 }
 
 extern "C" int fv3_adv_pe(fv3_ctx *c, double ptop, const double *ua, const double *va, const double *delp_before, double *omga) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !ua || !va || !delp_before || !omga) return fail("fv3_adv_pe: bad context/arguments");
   const Grid &g = c->g;
   if (g.grid_type >= 3) return fail("fv3_adv_pe: en1 / en2 are not defined for grid_type >= 3 (fv_grid_utils.F90:628)");
@@ -3878,6 +4029,7 @@ extern "C" int fv3_adv_pe(fv3_ctx *c, double ptop, const double *ua, const doubl
 }
 
 extern "C" int fv3_divg2_ext(fv3_ctx *c, double d_ext, const double *delp, const double *vt, double *divg2) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !delp || !vt || !divg2) return fail("fv3_divg2_ext: bad context/arguments");
   const Grid &g = c->g;
   RT(grp_stream_op(c, 1, divg2, nullptr, sizeof(double) * g.nA(), 0));
@@ -3892,15 +4044,18 @@ static int one_grad_p_impl(fv3_ctx *c, double *u, double *v, const double *pk, c
                            double ptk, double beta, double *du, double *dv, const double *delp = nullptr, double gz_scale = 1.0);
 extern "C" int fv3_one_grad_p(fv3_ctx *c, double *u, double *v, const double *pk, const double *gz, const double *divg2,
                               double dt, double ptk) {
+  FV3_ENTRY(c);
   return one_grad_p_impl(c, u, v, pk, gz, divg2, dt, ptk, 0., nullptr, nullptr);
 }
 extern "C" int fv3_one_grad_p_nh(fv3_ctx *c, double *u, double *v, const double *pk, const double *gz, const double *divg2,
                                  const double *delp, double dt, double ptop, double gz_scale) {
+  FV3_ENTRY(c);
   if (!delp) return fail("fv3_one_grad_p_nh: delp is required (the layer weights are a2b_ord4 of delp)");
   return one_grad_p_impl(c, u, v, pk, gz, divg2, dt, ptop, 0., nullptr, nullptr, delp, gz_scale);
 }
 extern "C" int fv3_grad1_p_update(fv3_ctx *c, const double *divg2, double *u, double *v, const double *pk, const double *gz, double dt,
                                   double ptk, double beta, double *du, double *dv) {
+  FV3_ENTRY(c);
   if (!du || !dv) return fail("fv3_grad1_p_update: du, dv (U / V x npz, zero before the first call) are required");
   return one_grad_p_impl(c, u, v, pk, gz, divg2, dt, ptk, beta, du, dv);
 }
@@ -3955,6 +4110,7 @@ extern "C" int fv3_copy_a_to_cc(fv3_ctx *c, const double *src, double *dst, int 
 }
 
 extern "C" int fv3_pk3_halo(fv3_ctx *c, double ptop, double akap, double *pk3, const double *delp, int use_logp) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_pk3_halo: context has no grid");
   Pk3Halo kf{c->g, c->g.npz, use_logp, ptop, akap, delp, pk3};
   Dim3 gr;
@@ -3966,6 +4122,7 @@ extern "C" int fv3_pk3_halo(fv3_ctx *c, double ptop, double akap, double *pk3, c
 }
 
 extern "C" int fv3_pe_halo(fv3_ctx *c, double ptop, double *pe, const double *delp) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_pe_halo: context has no grid");
   PeHalo kf{c->g, c->g.npz, ptop, delp, pe};
   RT(launch_c(c, "pe_halo", col_grid((c->g.nx + 2) * (c->g.ny + 2)), kf));
@@ -3975,6 +4132,7 @@ extern "C" int fv3_pe_halo(fv3_ctx *c, double ptop, double *pe, const double *de
 extern "C" int fv3_geopk(fv3_ctx *c, double ptop, double akap, double cp_air, double ptk, double *pe, double *peln,
                          const double *delp, double *pk, double *gz, const double *hs, const double *pt, double *pkz,
                          int CG) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_geopk: context has no grid");
   const int e = CG ? 1 : 2;
   const int ncol = (c->g.nx + 2 * e) * (c->g.ny + 2 * e);
@@ -4042,6 +4200,7 @@ extern "C" int fv3_compute_total_energy(fv3_ctx *c, const fv3_remap_params *p, i
                                         const double *v, const double *w, const double *delz, const double *pt,
                                         const double *delp, const double *q, const double *qc, const double *pe,
                                         const double *peln, const double *phis, double *te_2d) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !p) return fail("fv3_compute_total_energy: bad context/arguments");
   if (!u || !v || !pt || !delp || !phis || !te_2d) return fail("fv3_compute_total_energy: null argument");
   if (p->hydrostatic ? (!pe || !peln) : (!w || !delz)) return fail("fv3_compute_total_energy: null argument of the branch");
@@ -4061,6 +4220,7 @@ extern "C" int fv3_energy_fixer_sums(fv3_ctx *c, const fv3_remap_params *p, int 
                                      const double *q, const double *pe, const double *peln, const double *phis,
                                      const double *pkz, const double *pk, const double *te0_2d, double *te_2d,
                                      double *zsum1, double *zsum0) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !p) return fail("fv3_energy_fixer_sums: bad context/arguments");
   if (!delp || !pkz || !zsum1 || (p->hydrostatic && (!pk || !zsum0))) return fail("fv3_energy_fixer_sums: null argument");
   if (!only_sums) {
@@ -4080,6 +4240,7 @@ extern "C" int fv3_energy_fixer_sums(fv3_ctx *c, const fv3_remap_params *p, int 
 
 extern "C" int fv3_remap_finish(fv3_ctx *c, const fv3_remap_params *p, double dtmp, double *pt, const double *pkz,
                                 const double *q) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !p || !pt || !pkz) return fail("fv3_remap_finish: bad context/arguments");
   if (p->sphum > 0 && !q) return fail("fv3_remap_finish: sphum > 0 needs the tracers");
   RemapPar rp;
@@ -4115,6 +4276,7 @@ extern "C" int fv3_lagrangian_to_eulerian(fv3_ctx *c, const fv3_remap_params *p,
                                           double *pe, double *delp, double *pkz, double *pk, double *u, double *v,
                                           double *w, double *delz, double *pt, double *q, double *peln, double *omga,
                                           const double *ws) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !p) return fail("fv3_lagrangian_to_eulerian: bad context/arguments");
   if (!c->akbk_ready) return fail("fv3_lagrangian_to_eulerian: call fv3_set_ak_bk first");
   if (p->nq < 0 || p->nq > 64) return fail("fv3_lagrangian_to_eulerian: nq out of range");
@@ -4214,10 +4376,9 @@ extern "C" int fv3_lagrangian_to_eulerian(fv3_ctx *c, const fv3_remap_params *p,
   const size_t need = slab * (size_t)(8 + kSetSlabs * nsets);
   if (c->remap_scr_n < need) {
     RT(grp_flush_all());   // queued launches of a face group may still hold the old pointer
-    if (c->remap_scr) rt_free(c->remap_scr);
-    c->remap_scr = nullptr;
+    work_free(c, &c->remap_scr);
     c->remap_scr_n = 0;
-    RT(rt_malloc((void **)&c->remap_scr, need * sizeof(double)));
+    RT(work_alloc(c, "remap_scr", 0, &c->remap_scr, need));
     c->remap_scr_n = need;
   }
   double *co = c->remap_scr, *sets = c->remap_scr + 8 * slab;
@@ -4276,13 +4437,14 @@ extern "C" int fv3_lagrangian_to_eulerian(fv3_ctx *c, const fv3_remap_params *p,
 // ================================================================================================
 static int need_trc(fv3_ctx *c) {
   const int npz = c->g.npz;
-  if (!c->trc_d) RT(rt_malloc((void **)&c->trc_d, sizeof(double) * 3 * npz));   // cmax, frac, trdm per level (cubed deln)
+  if (!c->trc_d) RT(work_alloc(c, "trc_d", 0, &c->trc_d, (size_t)3 * npz));   // cmax, frac, trdm per level (cubed deln)
   if (!c->trc_i) RT(rt_malloc((void **)&c->trc_i, sizeof(int) * 2 * npz));      // ksplt, nord_tr per level
   return 0;
 }
 
 extern "C" int fv3_tracer_2d_prep(fv3_ctx *c, int q_split, const double *cx, const double *cy, double *xfx,
                                   double *yfx, double *cmax_host) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_tracer_2d_prep: context has no grid");
   if (need_trc(c)) return 1;
   const Grid &g = c->g;
@@ -4303,6 +4465,7 @@ extern "C" int fv3_tracer_2d_prep(fv3_ctx *c, int q_split, const double *cx, con
 
 extern "C" int fv3_tracer_2d_scale(fv3_ctx *c, const double *frac_host, double *cx, double *xfx, double *mfx,
                                    double *cy, double *yfx, double *mfy) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !frac_host) return fail("fv3_tracer_2d_scale: bad context/arguments");
   if (need_trc(c)) return 1;
   const Grid &g = c->g;
@@ -4325,6 +4488,7 @@ extern "C" int fv3_tracer_2d_step(fv3_ctx *c, int it, int nsplt, const int *kspl
                                   double trdm, const double *q, double *q_out, const double *dp1, double *dp1_out,
                                   const double *mfx, const double *mfy, const double *cx, const double *cy,
                                   const double *xfx, const double *yfx) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !ksplt_host) return fail("fv3_tracer_2d_step: bad context/arguments");
   if (!tp_ord_supported(hord)) return fail("fv3_tracer_2d_step: hord=%d not supported -- " FV3_HORD_TABLE, hord);
   if (q == q_out || dp1 == dp1_out) return fail("fv3_tracer_2d_step: *_out buffers must not alias the inputs");
@@ -4344,6 +4508,7 @@ extern "C" int fv3_tracer_2d_step(fv3_ctx *c, int it, int nsplt, const int *kspl
 extern "C" int fv3_d_sw_inline_q(fv3_ctx *c, int nq, int hord_tr, int nord_t, double damp_t, const double *q, double *q_out,
                                  const double *delp_old, const double *delp_new, const double *fx, const double *fy,
                                  const double *crx, const double *cry, const double *xfx, const double *yfx) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_d_sw_inline_q: context has no grid");
   if (nq < 1 || !q || !q_out || !delp_old || !delp_new || !fx || !fy || !crx || !cry || !xfx || !yfx)
     return fail("fv3_d_sw_inline_q: null argument");
@@ -4374,6 +4539,7 @@ extern "C" int fv3_d_sw_inline_q(fv3_ctx *c, int nq, int hord_tr, int nord_t, do
 }
 
 extern "C" int fv3_flux_accum(fv3_ctx *c, double *mfx, double *mfy, const double *fx, const double *fy) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || !mfx || !mfy || !fx || !fy) return fail("fv3_flux_accum: bad context/arguments");
   const Grid &g = c->g;
   FluxAccum kf{g, mfx, mfy, fx, fy};
@@ -4387,6 +4553,7 @@ extern "C" int fv3_flux_accum(fv3_ctx *c, double *mfx, double *mfy, const double
 }
 
 extern "C" int fv3_fill2d_mass(fv3_ctx *c, int nk, const double *q, const double *delp, double *qt) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || nk < 1 || !q || !delp || !qt) return fail("fv3_fill2d_mass: bad context/arguments");
   const Grid &g = c->g;
   Fill2dMass kf{g, q, delp, qt};
@@ -4398,6 +4565,7 @@ extern "C" int fv3_fill2d_mass(fv3_ctx *c, int nk, const double *q, const double
   return 0;
 }
 extern "C" int fv3_fill2d_apply(fv3_ctx *c, int nk, const double *qt, const double *delp, double *q) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready || nk < 1 || !q || !delp || !qt) return fail("fv3_fill2d_apply: bad context/arguments");
   const Grid &g = c->g;
   Fill2dApply kf{g, qt, delp, q};
@@ -4411,6 +4579,7 @@ extern "C" int fv3_fill2d_apply(fv3_ctx *c, int nk, const double *qt, const doub
 
 extern "C" int fv3_neg_adj3(fv3_ctx *c, const fv3_neg_adj_params *p, const double *peln, const double *delz, const double *delp,
                             double *pt, double *qv, double *ql, double *qr, double *qi, double *qs, double *qg, double *qa) {
+  FV3_ENTRY(c);
   if (!c || !c->grid_ready) return fail("fv3_neg_adj3: context has no grid");
   if (!p || !delp || !pt || !qv || !ql || !qr || !qi || !qs || !qg) return fail("fv3_neg_adj3: null parameters / field");
   if (p->hydrostatic && !peln) return fail("fv3_neg_adj3: hydrostatic needs peln");

@@ -21,12 +21,24 @@ struct Dim3 {
   unsigned x, y, z;
 };
 
+// FV3_MI355X_POISON (fv3_api.hip sets this at every compute entry): the emulated LDS holds the poison pattern at the start of
+// every workgroup, not zeros once per launch -- a kernel that reads LDS it has not written, or what another workgroup left there,
+// shows.  (On the GPU LDS cannot be poisoned from outside a kernel.)
+inline int &rt_lds_poison() {
+  static int on = 0;
+  return on;
+}
 template <class F>
 inline int launch(Dim3 grid, size_t lds_doubles, stream_t, const F &f) {
   std::vector<double> lds(lds_doubles + 1, 0.);
+  const bool poison = rt_lds_poison() != 0;
   for (unsigned z = 0; z < grid.z; z++)
     for (unsigned y = 0; y < grid.y; y++)
-      for (unsigned x = 0; x < grid.x; x++) f((int)x, (int)y, (int)z, 0, lds.data());  // order irrelevant here
+      for (unsigned x = 0; x < grid.x; x++) {  // order irrelevant here
+        if (poison)
+          for (size_t i = 0; i < lds.size(); i++) lds[i] = ((i & 1) ? -1.0e30 : 1.0e30) * (double)(1 + (int)(i % 7));
+        f((int)x, (int)y, (int)z, 0, lds.data());
+      }
   return 0;
 }
 template <class F>

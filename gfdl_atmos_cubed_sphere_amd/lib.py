@@ -371,8 +371,9 @@ class Context:
             b.free()
         self._buffers.clear()
         if self.h:
-            self.lib.dll.fv3_destroy(self.h)
+            rc = self.lib.dll.fv3_destroy(self.h)   # everything is freed whatever the status
             self.h = None
+            self.lib.check(rc, "fv3_destroy")       # FV3_MI355X_POISON: a damaged guard band of a work array
 
     # -- operators (argument names follow the reference routines) ------------------------------------
     def fv_tp_2d(self, q, crx, cry, hord, fx, fy, xfx, yfx, ra_x=None, ra_y=None, mfx=None, mfy=None, mass=None,

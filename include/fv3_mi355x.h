@@ -83,6 +83,9 @@ typedef struct fv3_grid_cubed {
 
 const char *fv3_last_error(void);
 int fv3_create(const fv3_domain *dom, fv3_ctx **out);
+/* Frees everything the context holds.  Under FV3_MI355X_POISON=1 (docs/SWITCHES.md) it first checks the guard bands of the work
+ * arrays and, after freeing, returns non-zero when one is damaged (fv3_last_error names the array and the first offset); fv3_sync
+ * makes the same check. */
 int fv3_destroy(fv3_ctx *ctx);
 /* stream: a hipStream_t (NULL = default stream). */
 int fv3_set_stream(fv3_ctx *ctx, void *stream);
@@ -207,7 +210,14 @@ int fv3_dsw_levels_upload(fv3_ctx *ctx, const fv3_dsw_levels *lv);
  *         does not read it -- dyn_core.F90:798-812 does when d_con > 1e-5 or do_diss_est); delpc (A, the
  *         saved divergence on is:ie+1 x js:je+1; may be NULL).
  * The reference's clobbering of uc, vc, divg_d as scratch (sw_core.F90:1394-1408) is not reproduced:
- * those arrays are left unchanged. */
+ * those arrays are left unchanged.
+ * Call order: none of the compute routines of this header reads what another one left in the library's work arrays (the carried-slots
+ * table of fv3_api.hip has no row), so any routine may be called between any two others -- between fv3_d_sw_interior and fv3_d_sw_rest,
+ * between fv3_d_sw and fv3_d_sw_inline_q / fv3_heat_source_accum, between fv3_tracer_2d_prep, _scale and the _step calls.  What those
+ * sequences hand on travels in the caller's arrays, which the caller must leave alone in between, and in the per-level tables
+ * (fv3_dsw_levels_upload; ksplt of fv3_tracer_2d_step, uploaded with it = 1 and read by it > 1: no other fv3_tracer_2d_step /
+ * fv3_d_sw_inline_q sequence in between).  FV3_MI355X_POISON=1 (docs/SWITCHES.md) holds the library to this: every work array is
+ * poisoned at the head of every compute routine and lies between guard bands that fv3_sync and fv3_destroy check. */
 int fv3_d_sw(fv3_ctx *ctx, const fv3_dsw_params *p, double *delpc, const double *delp, const double *pt,
              const double *u, const double *v, const double *w, const double *uc, const double *vc,
              const double *ua, const double *va, const double *divg_d, double *mfx, double *mfy, double *cx,
@@ -356,7 +366,8 @@ int fv3_mix_dp(fv3_ctx *ctx, int hydrostatic, double *w, double *delp, double *p
 
 /* Riem_Solver_c -- model/nh_utils.F90:323, call site model/dyn_core.F90:531 (a_imp > 0.5: SIM1_solver; a_imp < -0.01: SIM3p0_solver;
  * otherwise RIM_2D with cn->m_split sub-steps, nh_utils.F90:449-459).
- * hs, ws: A; w3 (=omga), pt (=ptc), delp (=delpc): A x npz; gz (in/out), pef (=pkc, out): A x (npz+1). */
+ * hs, ws: A; w3 (=omga), pt (=ptc), delp (=delpc): A x npz; gz (in/out), pef (=pkc, out): A x (npz+1), both written on
+ * is-1:ie+1 x js-1:je+1 and nowhere else. */
 int fv3_riem_solver_c(fv3_ctx *ctx, double dt, const fv3_nh_consts *cn, const double *hs, const double *w3,
                       const double *pt, const double *delp, double *gz, double *pef, const double *ws);
 
@@ -369,8 +380,8 @@ int fv3_update_dz_d(fv3_ctx *ctx, int hord, const double *zs, const double *zh_i
                     double rdt);
 
 /* Riem_Solver3 -- model/nh_core.F90:47, call site model/dyn_core.F90:932 (a_imp > 0.999: SIM1_solver, else
- * SIM_solver).  w, zh in/out; delz (CC x npz), ppe (=pkc), pk3 (A x (npz+1)) out; pe (is-1:ie+1, npz+1,
- * js-1:je+1), pk (CC x (npz+1)), peln (is:ie, npz+1, js:je) written when last_call. */
+ * SIM_solver).  w, zh in/out, ppe (=pkc) out: written on the compute domain and nowhere else; delz (CC x npz), pk3 (A x (npz+1)) out;
+ * pe (is-1:ie+1, npz+1, js-1:je+1), pk (CC x (npz+1)), peln (is:ie, npz+1, js:je) written when last_call, untouched otherwise. */
 int fv3_riem_solver3(fv3_ctx *ctx, double dt, const fv3_nh_consts *cn, const double *zs, double *w, double *delz,
                      const double *pt, const double *delp, double *zh, double *pe, double *ppe, double *pk3,
                      double *pk, double *peln, const double *ws, int use_logp, int last_call, int fp_out);

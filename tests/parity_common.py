@@ -16,6 +16,7 @@ from fields import smooth_state
 from gfdl_atmos_cubed_sphere_amd.grid import doubly_periodic, perturbed
 from gfdl_atmos_cubed_sphere_amd.layout import Bounds, periodic_fill
 from gfdl_atmos_cubed_sphere_amd.lib import Context
+from memory_contract import host_out, out_array
 from test_oracle_properties import _courant, default_levels
 
 TOL = 1e-14
@@ -42,7 +43,8 @@ def assert_close(name, got, ref, tol=TOL):
 
 
 # ------------------------------------------------------------------------------------------------
-def check_fv_tp_2d(lib, hord, nx=40, ny=19, nk=3, perturb=True, mode="plain", nord=-1, damp_c=0.0, seed=5):
+def check_fv_tp_2d(lib, hord, nx=40, ny=19, nk=3, perturb=True, mode="plain", nord=-1, damp_c=0.0, seed=5, out_fill=0.0):
+    """out_fill: what the arrays the header calls `out` hold before the call (memory_contract.py); fx, fy are compared whole"""
     bd = Bounds(1, nx, 1, ny)
     g = make_grid(bd, perturb)
     rng = np.random.default_rng(seed)
@@ -75,7 +77,7 @@ def check_fv_tp_2d(lib, hord, nx=40, ny=19, nk=3, perturb=True, mode="plain", no
     try:
         d = {n: ctx.from_host(a) for n, a in arrs.items()}
         dq = ctx.from_host(q)
-        dfx, dfy = ctx.zeros("FX", nk), ctx.zeros("FY", nk)
+        dfx, dfy = out_array(ctx, "FX", nk, out_fill), out_array(ctx, "FY", nk, out_fill)
         ctx.fv_tp_2d(dq, d["crx"], d["cry"], hord, dfx, dfy, d["xfx"], d["yfx"], d["ra_x"], d["ra_y"],
                      d["mfx"] if use_mf else None, d["mfy"] if use_mf else None, d["mass"] if use_mass else None,
                      nord, damp_c, nk=nk)
@@ -107,10 +109,10 @@ def run_c_sw_oracle(g, bd, npz, st, dt2, hydrostatic, nord=1):
     return f
 
 
-def run_c_sw_lib(ctx, bd, npz, st, dt2, hydrostatic, nord=1):
+def run_c_sw_lib(ctx, bd, npz, st, dt2, hydrostatic, nord=1, out_fill=0.0):
     d = {k: ctx.from_host(v) for k, v in st.items()}
     for n, kind in CSW_OUT:
-        d[n] = ctx.zeros(kind, npz)
+        d[n] = out_array(ctx, kind, npz, out_fill)
     ctx.c_sw(d["delpc"], d["delp"], d["ptc"], d["pt"], d["u"], d["v"], d.get("w"), d["uc"], d["vc"], d["ua"],
              d["va"], None if hydrostatic else d["wc"], d["ut"], d["vt"], d["divg_d"], nord, dt2, hydrostatic)
     return d
@@ -150,20 +152,24 @@ def degenerate_state(bd, npz, hydrostatic, kind):
     return st
 
 
-def check_c_sw(lib, nx=40, ny=19, npz=3, hydrostatic=False, perturb=True, dt=6.0, state=None):
+def check_c_sw(lib, nx=40, ny=19, npz=3, hydrostatic=False, perturb=True, dt=6.0, state=None, out_fill=0.0, nord=1):
+    """nord = 0: the header says divg_d is not written -- it comes back bit for bit as it went in"""
     bd = Bounds(1, nx, 1, ny)
     g = make_grid(bd, perturb)
     st = degenerate_state(bd, npz, hydrostatic, state) if state else smooth_state(bd, npz, hydrostatic=hydrostatic)
-    ref = run_c_sw_oracle(g, bd, npz, st, 0.5 * dt, hydrostatic)
+    ref = run_c_sw_oracle(g, bd, npz, st, 0.5 * dt, hydrostatic, nord=nord)
     ctx = Context(g, npz, lib=lib)
     worst = 0.0
     try:
-        d = run_c_sw_lib(ctx, bd, npz, st, 0.5 * dt, hydrostatic)
+        d = run_c_sw_lib(ctx, bd, npz, st, 0.5 * dt, hydrostatic, nord=nord, out_fill=out_fill)
         rng_ = csw_valid_ranges(bd)
         for n, kind in CSW_OUT:
             if hydrostatic and n == "wc":
                 continue
             got = d[n].download()
+            if n == "divg_d" and nord == 0:
+                assert np.array_equal(got, host_out(got.shape, out_fill)), "c_sw, nord = 0: divg_d was written"
+                continue
             r = rng_[n]
             worst = max(worst, assert_close(n, bd.view(got, kind, *r), bd.view(ref[n], kind, *r)))
     finally:
@@ -175,8 +181,11 @@ def check_c_sw(lib, nx=40, ny=19, npz=3, hydrostatic=False, perturb=True, dt=6.0
 
 
 def check_d_sw(lib, nx=40, ny=19, npz=4, hydrostatic=False, perturb=True, par_over=None, lev_over=None,
-               flags=None, use_cond=False, phases=False, state=None):
-    """c_sw (oracle) -> periodic halo of uc, vc, divg_d -> d_sw by oracle and by the library."""
+               flags=None, use_cond=False, phases=False, state=None, out_fill=0.0, poison_inputs=()):
+    """c_sw (oracle) -> periodic halo of uc, vc, divg_d -> d_sw by oracle and by the library.
+    out_fill: what the `out` arrays hold before the call (memory_contract.py); crx, cry, xfx, yfx are compared whole, so the oracle's
+    hold the same.  poison_inputs: inputs the header says this configuration does not read ("ua", "va", "divg_d"): the library gets
+    them filled with the pattern, the oracle the real ones."""
     bd = Bounds(1, nx, 1, ny)
     g = make_grid(bd, perturb)
     for k, v in (flags or {}).items():
@@ -197,8 +206,9 @@ def check_d_sw(lib, nx=40, ny=19, npz=4, hydrostatic=False, perturb=True, par_ov
             periodic_fill(bd, f["q_con"][:, :, k], "A")
     for n, kind in (("mfx", "FX"), ("mfy", "FY"), ("cx", "CX"), ("cy", "CY")):
         f[n] = np.asfortranarray(rng.uniform(-1, 1, bd.shape(kind, npz)))  # non-zero: accumulation is checked
-    for n, kind in (("crx", "CX"), ("cry", "CY"), ("xfx", "CX"), ("yfx", "CY"), ("heat_source", "CC"),
-                    ("diss_est", "CC")):
+    for n, kind in (("crx", "CX"), ("cry", "CY"), ("xfx", "CX"), ("yfx", "CY")):
+        f[n] = host_out(bd.shape(kind, npz), out_fill)
+    for n, kind in (("heat_source", "CC"), ("diss_est", "CC")):      # (the oracle accumulates into these)
         f[n] = bd.zeros(kind, npz)
     lev = default_levels(npz, **(lev_over or {}))
     inp = {k: v.copy(order="F") for k, v in f.items()}
@@ -214,9 +224,11 @@ def check_d_sw(lib, nx=40, ny=19, npz=4, hydrostatic=False, perturb=True, par_ov
     try:
         ctx.dsw_levels(lev)
         d = {k: ctx.from_host(v) for k, v in inp.items() if k not in ("heat_source", "diss_est")}
-        out = {n: ctx.zeros(kind, npz) for n, kind in (("delp_out", "A"), ("pt_out", "A"), ("u_out", "U"),
-                                                       ("v_out", "V"), ("w_out", "A"), ("q_con_out", "A"),
-                                                       ("heat_s", "CC"), ("diss_e", "CC"), ("delpc_o", "A"))}
+        for n in poison_inputs:
+            d[n].upload(host_out(d[n].shape, "pattern"))
+        out = {n: out_array(ctx, kind, npz, out_fill) for n, kind in (("delp_out", "A"), ("pt_out", "A"), ("u_out", "U"),
+                                                                      ("v_out", "V"), ("w_out", "A"), ("q_con_out", "A"),
+                                                                      ("heat_s", "CC"), ("diss_e", "CC"), ("delpc_o", "A"))}
         args = (par, out["delpc_o"], d["delp"], d["pt"], d["u"], d["v"], d.get("w"), d["uc"], d["vc"], d["ua"],
                 d["va"], d["divg_d"], d["mfx"], d["mfy"], d["cx"], d["cy"], d["crx"], d["cry"], d["xfx"], d["yfx"],
                 d.get("q_con"), out["delp_out"], out["pt_out"], out["u_out"], out["v_out"],

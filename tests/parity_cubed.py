@@ -10,9 +10,11 @@ import parity_common as P
 from gfdl_atmos_cubed_sphere_amd import lib as L
 from gfdl_atmos_cubed_sphere_amd.lib import Context
 from gfdl_atmos_cubed_sphere_amd.synthetic import CSW_OUT
+from memory_contract import host_out, out_array
 
 
-def check_c_sw(lib, npx=13, npz=3, hydrostatic=False, faces=range(6), dt2=300.0, nord=1):
+def check_c_sw(lib, npx=13, npz=3, hydrostatic=False, faces=range(6), dt2=300.0, nord=1, out_fill=0.0):
+    """out_fill (here and below): what the `out` arrays hold before the call (memory_contract.py)"""
     cs, gs, st = CC.global_state(npx, npz, hydrostatic)
     worst = 0.0
     for t in faces:
@@ -25,7 +27,7 @@ def check_c_sw(lib, npx=13, npz=3, hydrostatic=False, faces=range(6), dt2=300.0,
         try:
             d = {k: ctx.from_host(v) for k, v in st[t].items()}
             for n, kind in CSW_OUT:
-                d[n] = ctx.zeros(kind, npz)
+                d[n] = out_array(ctx, kind, npz, out_fill)
             ctx.c_sw(d["delpc"], d["delp"], d["ptc"], d["pt"], d["u"], d["v"], d.get("w"), d["uc"], d["vc"], d["ua"], d["va"],
                      d.get("wc") if not hydrostatic else None, d["ut"], d["vt"], d["divg_d"], nord, dt2, hydrostatic)
             rng = P.csw_valid_ranges(bd)
@@ -42,7 +44,7 @@ def check_c_sw(lib, npx=13, npz=3, hydrostatic=False, faces=range(6), dt2=300.0,
     return worst
 
 
-def check_fv_tp_2d(lib, hord, npx=13, nk=3, faces=range(6), mass_flux=False, seed=4, nord=-1, damp_c=0.0):
+def check_fv_tp_2d(lib, hord, npx=13, nk=3, faces=range(6), mass_flux=False, seed=4, nord=-1, damp_c=0.0, out_fill=0.0):
     """fv_tp_2d on every face: q and the Courant numbers / area fluxes of a real c_sw -> d_sw step of the oracle"""
     cs, gs, before, after = CC.oracle_pair(npx, nk, dt=600.0, hydrostatic=True)
     rng = np.random.default_rng(seed)
@@ -69,7 +71,7 @@ def check_fv_tp_2d(lib, hord, npx=13, nk=3, faces=range(6), mass_flux=False, see
             fx_ref[:, :, k], fy_ref[:, :, k] = fx, fy
         ctx = Context(g, nk, lib=lib)
         try:
-            dfx, dfy = ctx.zeros("FX", nk), ctx.zeros("FY", nk)
+            dfx, dfy = out_array(ctx, "FX", nk, out_fill), out_array(ctx, "FY", nk, out_fill)
             ctx.fv_tp_2d(ctx.from_host(CCq), ctx.from_host(a["crx"]), ctx.from_host(a["cry"]), hord, dfx, dfy, ctx.from_host(a["xfx"]),
                          ctx.from_host(a["yfx"]), ctx.from_host(ra_x), ctx.from_host(ra_y),
                          None if mfx is None else ctx.from_host(mfx), None if mfy is None else ctx.from_host(mfy),
@@ -82,7 +84,7 @@ def check_fv_tp_2d(lib, hord, npx=13, nk=3, faces=range(6), mass_flux=False, see
 
 
 def check_d_sw(lib, npx=13, npz=3, hydrostatic=True, faces=range(6), dt=600.0, par_over=None, flags=None, use_cond=False,
-               grid_flags=None):
+               grid_flags=None, out_fill=0.0):
     """c_sw (oracle) on every face -> emulated halo updates of uc, vc, divg_d -> d_sw by the oracle and by the library.
     grid_flags: do_diss_est / prevent_diss_cooling of the gridstruct (the sphere's grids are shared: set, run, restore)"""
     if grid_flags:
@@ -92,7 +94,7 @@ def check_d_sw(lib, npx=13, npz=3, hydrostatic=True, faces=range(6), dt=600.0, p
             for k, v in grid_flags.items():
                 setattr(g, k, v)
         try:
-            return check_d_sw(lib, npx, npz, hydrostatic, faces, dt, par_over, flags, use_cond)
+            return check_d_sw(lib, npx, npz, hydrostatic, faces, dt, par_over, flags, use_cond, out_fill=out_fill)
         finally:
             for g, o in zip(gs_, old):
                 for k, v in o.items():
@@ -113,10 +115,11 @@ def check_d_sw(lib, npx=13, npz=3, hydrostatic=True, faces=range(6), dt=600.0, p
         try:
             ctx.dsw_levels(lev)
             d = {k: ctx.from_host(v) for k, v in b.items() if k not in ("wc",)}
-            for n, kind in (("mfx", "FX"), ("mfy", "FY"), ("cx", "CX"), ("cy", "CY"), ("crx", "CX"), ("cry", "CY"), ("xfx", "CX"),
-                            ("yfx", "CY")):
+            for n, kind in (("mfx", "FX"), ("mfy", "FY"), ("cx", "CX"), ("cy", "CY")):      # the flux capacitors: accumulated
                 d[n] = ctx.zeros(kind, npz)
-            out = {n: ctx.zeros(kind, npz) for n, kind in (("delp_out", "A"), ("pt_out", "A"), ("u_out", "U"), ("v_out", "V"),
+            for n, kind in (("crx", "CX"), ("cry", "CY"), ("xfx", "CX"), ("yfx", "CY")):
+                d[n] = out_array(ctx, kind, npz, out_fill)
+            out = {n: out_array(ctx, kind, npz, out_fill) for n, kind in (("delp_out", "A"), ("pt_out", "A"), ("u_out", "U"), ("v_out", "V"),
                                                            ("w_out", "A"), ("heat_s", "CC"), ("diss_e", "CC"), ("delpc_o", "A"), ("qc_out", "A"))}
             ctx.d_sw(par, out["delpc_o"], d["delp"], d["pt"], d["u"], d["v"], d.get("w"), d["uc"], d["vc"], d["ua"], d["va"],
                      d["divg_d"], d["mfx"], d["mfy"], d["cx"], d["cy"], d["crx"], d["cry"], d["xfx"], d["yfx"], d.get("q_con"),
@@ -392,7 +395,7 @@ def check_sphere_properties(lib, npx=97, npz=127, hydrostatic=False, k_split=1, 
     return out
 
 
-def check_tracer_2d(lib, npx=13, npz=4, nq=3, hord=8, q_split=0, courant_scale=1.0, dt=600.0, nord_tr=0, trdm=0.0):
+def check_tracer_2d(lib, npx=13, npz=4, nq=3, hord=8, q_split=0, courant_scale=1.0, dt=600.0, nord_tr=0, trdm=0.0, out_fill=0.0):
     """tracer_2d on the whole sphere with the mass fluxes / Courant numbers of one c_sw -> d_sw step of the oracle; a
     courant_scale > 1 makes the levels sub-cycle (nsplt > 1, different ksplt per level)"""
     from gfdl_atmos_cubed_sphere_amd.cubed_dyn import CubeHaloAdapter, MultiContext
@@ -417,8 +420,10 @@ def check_tracer_2d(lib, npx=13, npz=4, nq=3, hord=8, q_split=0, courant_scale=1
     try:
         halo = CubeHaloAdapter(mctx, npx, topo=CC.product_topo(npx))
         d = {n: mctx.from_host([x[n] for x in inp]) for n in ("q", "dp1", "mfx", "mfy", "cx", "cy")}
-        d["q_nxt"], d["dp1_nxt"] = mctx.from_host([x["q"] * 0 for x in inp]), mctx.zeros("A", npz)
-        d["xfx"], d["yfx"] = mctx.zeros("CX", npz), mctx.zeros("CY", npz)
+        d["q_nxt"] = mctx.from_host([host_out(x["q"].shape, out_fill) for x in inp])
+        d["dp1_nxt"], d["xfx"], d["yfx"] = (mctx.from_host([host_out(bd.shape(kind, npz), out_fill) for _ in inp]) for kind in ("A", "CX", "CY"))
+        if out_fill == "pattern":   # (prep is idempotent) a poisoned cmax must never size the sub-cycle loop of tracer_2d
+            assert np.all(np.abs(np.stack(mctx.tracer_2d_prep(q_split, d["cx"], d["cy"], d["xfx"], d["yfx"]))) < 1.0e3), "cmax"
         q, dp1, ns = tracer_2d(mctx, halo, d["q"], d["q_nxt"], d["dp1"], d["dp1_nxt"], d["mfx"], d["mfy"], d["cx"], d["cy"],
                                d["xfx"], d["yfx"], nq, hord, q_split, nord_tr, trdm)
         assert ns == nsplt, (ns, nsplt)

@@ -12,7 +12,8 @@ from gfdl_atmos_cubed_sphere_amd.tracer2d import tracer_2d
 from test_oracle_properties import run_pair
 
 
-def check_tracer_2d(lib, nx=40, ny=19, npz=4, nq=3, hord=8, q_split=0, trdm=0.0, nord_tr=1, big_courant=False, reverse=False):
+def check_tracer_2d(lib, nx=40, ny=19, npz=4, nq=3, hord=8, q_split=0, trdm=0.0, nord_tr=1, big_courant=False, reverse=False, out_fill=0.0):
+    from memory_contract import host_out, out_array, unchanged_outside  # noqa: F401
     bd = Bounds(1, nx, 1, ny)
     g = P.make_grid(bd, False)
     before, after = run_pair(bd, npz, g, True, dt=8.0)    # oracle c_sw + d_sw: realistic mfx, mfy, cx, cy
@@ -31,9 +32,11 @@ def check_tracer_2d(lib, nx=40, ny=19, npz=4, nq=3, hord=8, q_split=0, trdm=0.0,
     ctx = Context(g, npz, lib=lib)
     try:
         halo = HaloExchanger(ctx, 1, 1, 0, 1)
-        d = dict(q=ctx.from_host(q), q_nxt=ctx.from_host(np.zeros_like(q)), dp1=ctx.from_host(dp1),
-                 dp1_nxt=ctx.from_host(np.zeros_like(dp1)), mfx=ctx.from_host(mfx), mfy=ctx.from_host(mfy),
-                 cx=ctx.from_host(cx), cy=ctx.from_host(cy), xfx=ctx.zeros("CX", npz), yfx=ctx.zeros("CY", npz))
+        d = dict(q=ctx.from_host(q), q_nxt=ctx.from_host(host_out(q.shape, out_fill)), dp1=ctx.from_host(dp1),
+                 dp1_nxt=ctx.from_host(host_out(dp1.shape, out_fill)), mfx=ctx.from_host(mfx), mfy=ctx.from_host(mfy),
+                 cx=ctx.from_host(cx), cy=ctx.from_host(cy), xfx=out_array(ctx, "CX", npz, out_fill), yfx=out_array(ctx, "CY", npz, out_fill))
+        if out_fill == "pattern":   # (prep is idempotent) a poisoned cmax must never size the sub-cycle loop of tracer_2d
+            assert np.all(np.abs(ctx.tracer_2d_prep(q_split, d["cx"], d["cy"], d["xfx"], d["yfx"])) < 1.0e3), "cmax"
         qf, dpf, nsplt = tracer_2d(ctx, halo, d["q"], d["q_nxt"], d["dp1"], d["dp1_nxt"], d["mfx"], d["mfy"], d["cx"],
                                    d["cy"], d["xfx"], d["yfx"], nq, hord, q_split, nord_tr, trdm)
         assert nsplt == nsplt_ref, (nsplt, nsplt_ref)
@@ -52,7 +55,8 @@ def check_tracer_2d(lib, nx=40, ny=19, npz=4, nq=3, hord=8, q_split=0, trdm=0.0,
     return worst, nsplt
 
 
-def check_fill2d(lib, nx=40, ny=19, npz=4, grid=None, halo_fill=None):
+def check_fill2d(lib, nx=40, ny=19, npz=4, grid=None, halo_fill=None, out_fill=0.0):
+    from memory_contract import out_array, unchanged_outside
     """fill2D (fv_fill.F90:183-258) on a tracer with negative patches: the two kernels around the halo update of qt against the
     oracle's two halves; halo_fill(qt) fills the halo of a host array (default: the doubly periodic fill)"""
     bd = grid.bd if grid is not None else Bounds(1, nx, 1, ny)
@@ -70,7 +74,7 @@ def check_fill2d(lib, nx=40, ny=19, npz=4, grid=None, halo_fill=None):
     O.fill2d_apply(g, npz, qt, delp, ref)
     ctx = Context(g, npz, lib=lib)
     try:
-        d_q, d_dp, d_qt = ctx.from_host(q), ctx.from_host(delp), ctx.zeros("A", npz)
+        d_q, d_dp, d_qt = ctx.from_host(q), ctx.from_host(delp), out_array(ctx, "A", npz, out_fill)
         ctx.fill2d_mass(npz, d_q, d_dp, d_qt)
         h = d_qt.download()
         halo_fill(h)
@@ -79,6 +83,8 @@ def check_fill2d(lib, nx=40, ny=19, npz=4, grid=None, halo_fill=None):
         r = (bd.is_, bd.ie, bd.js, bd.je)
         got = d_q.download()
         assert np.any(got != q)
+        if out_fill == "pattern":
+            unchanged_outside("fill2d_apply q", q, got, "A", r, bd)
         # the filling moves mass between neighbours: the total of q delp area is what it was (to rounding)
         area = bd.view(g.m["area"], "A", *r)[:, :, None]
         m0, m1 = (bd.view(q, "A", *r) * bd.view(delp, "A", *r) * area).sum(), (bd.view(got, "A", *r) * bd.view(delp, "A", *r) * area).sum()
