@@ -28,6 +28,7 @@
 #include "nh_fast.h"
 #include "nh_alt.h"
 #include "neg_adj.h"
+#include "subgrid_z.h"
 #include "remap_kernels.h"
 #include "remap_fast.h"
 #include "tracer_kernels.h"
@@ -148,6 +149,13 @@ struct fv3_ctx {
   double *cg_dev;
   double *cs_scr[36];
   int *ones_i;    // npz ones, device (ksplt of the inline_q sub-step)
+  // fv_subgrid_z (subgrid_z.h): the columns' working copies of fv3_fv_subgrid_z, and what update_dwinds_phys reads of the gridstruct
+  // on the sphere (fv3_grid_upload_dwinds)
+  double *sg_wk = nullptr;
+  size_t sg_wk_n = 0;
+  DwindsGeom dw{};
+  double *dw_dev = nullptr;
+  bool dw_ready = false;
   std::vector<double> host_area;   // prt_maxmin: area on the host, and g_sum's global_area
   double global_area = 0.;
   int march_tj;          // rows per wavefront segment of the marching kernels
@@ -802,6 +810,8 @@ extern "C" int fv3_destroy(fv3_ctx *c) {
   for (auto &s : c->mflux) work_free(c, &s);
   for (auto &s : c->cs_scr) work_free(c, &s);
   if (c->cg_dev) rt_free(c->cg_dev);
+  work_free(c, &c->sg_wk);
+  if (c->dw_dev) rt_free(c->dw_dev);
   if (c->stream2) rt_stream_destroy(c->stream2);
   if (c->ev_fork) rt_event_destroy(c->ev_fork);
   if (c->ev_join) rt_event_destroy(c->ev_join);
@@ -4593,6 +4603,123 @@ extern "C" int fv3_neg_adj3(fv3_ctx *c, const fv3_neg_adj_params *p, const doubl
   grid.y = 1;
   grid.z = 1;
   RT(launch_p(c, "neg_adj3", grid, 0, kf));
+  return 0;
+}
+
+// ---- fv_subgrid_z: fv_sg_SHiELD and update_dwinds_phys (subgrid_z.h) -------------------------------------------------------------
+extern "C" int fv3_fv_subgrid_z(fv3_ctx *c, const fv3_sg_params *p, const double *delp, const double *pe, const double *peln,
+                                const double *pkz, double *ta, double *qa, double *ua, double *va, double *w, const double *delz,
+                                double *u_dt, double *v_dt) {
+  FV3_ENTRY(c);
+  if (!c || !c->grid_ready) return fail("fv3_fv_subgrid_z: context has no grid");
+  if (!p || !delp || !peln || !pkz || !ta || !qa || !ua || !va || !u_dt || !v_dt) return fail("fv3_fv_subgrid_z: null parameters / field");
+  if (p->hydrostatic && !pe) return fail("fv3_fv_subgrid_z: hydrostatic needs pe");
+  if (!p->hydrostatic && (!w || !delz)) return fail("fv3_fv_subgrid_z: nonhydrostatic needs w and delz");
+  const Grid &g = c->g;
+  if (p->fv_sg_adj <= 0) return fail("fv3_fv_subgrid_z: fv_sg_adj = %d: the relaxation time scale must be positive", p->fv_sg_adj);
+  if (p->k_bot_full < 1) return fail("fv3_fv_subgrid_z: k_bot_full = %d < 1", p->k_bot_full);
+  if (p->k_bot_full > g.npz && p->fv_sg_adj_weak <= 0)
+    return fail("fv3_fv_subgrid_z: k_bot_full = %d > npz = %d without fv_sg_adj_weak (the reference would overrun its columns)", p->k_bot_full, g.npz);
+  if (p->nq < 1) return fail("fv3_fv_subgrid_z: nq = %d < 1", p->nq);
+  if (p->nwat < 0) return fail("fv3_fv_subgrid_z: nwat = %d < 0", p->nwat);
+  if (!(p->dt > 0.)) return fail("fv3_fv_subgrid_z: dt must be positive");
+  // the species the branches of this nwat read (fv_sg.F90:214-249, :278-308); every nwat outside 0..4 takes the branches of nwat = 6
+  const int nw = p->nwat;
+  const struct { const char *name; int idx; bool need; } sp[6] = {
+      {"sphum", p->sphum, nw != 0},
+      {"liq_wat", p->liq_wat, nw >= 2},
+      {"rainwat", p->rainwat, nw >= 4},
+      {"ice_wat", p->ice_wat, nw == 3 || nw >= 5},
+      {"snowwat", p->snowwat, nw >= 5},
+      {"graupel", p->graupel, nw >= 5}};
+  for (const auto &s : sp)
+    if (s.need && (s.idx < 1 || s.idx > p->nq))
+      return fail("fv3_fv_subgrid_z: nwat = %d needs %s, whose index %d is outside 1..nq = %d", nw, s.name, s.idx, p->nq);
+  const int kbot = p->fv_sg_adj_weak <= 0 ? p->k_bot_full : g.npz;                 // :123-128
+  const double t_min = p->ptop < 2. ? 160. : 165.;                                  // :129-133, t1_min / t2_min
+  const double t_max = p->k_bot_full < (g.npz < 24 ? g.npz : 24) ? 315. : 325.;     // :135-139, t2_max / t3_max
+  const double fra_full = p->dt / (double)p->fv_sg_adj;                             // :163
+  const double fra_weak = p->fv_sg_adj_weak > 0 ? p->dt / (double)p->fv_sg_adj_weak : 0.;   // :164-168
+  // the working copies: 5 (hydrostatic) or 7 state fields + nq tracers, levels 1..kbot.  Grown when a call needs more; a launch that an
+  // fv3_group still holds in its queues carries the old pointer, so the queues run before the old array is freed
+  const size_t need = p->hydrostatic ? FvSubgridZ<true, 0>::work_doubles(g, kbot, p->nq) : FvSubgridZ<false, 0>::work_doubles(g, kbot, p->nq);
+  if (need > c->sg_wk_n) {
+    if (c->sg_wk) {
+      if (int rc = grp_flush_all()) return rc;
+      RT(rtf_sync(c->stream));
+    }
+    work_free(c, &c->sg_wk);
+    c->sg_wk_n = 0;
+    RT(work_alloc(c, "sg_wk", 0, &c->sg_wk, need));
+    c->sg_wk_n = need;
+  }
+  Dim3 grid;
+  grid.x = (unsigned)(((size_t)g.nx * g.ny + 255) / 256);
+  grid.y = 1;
+  grid.z = 1;
+  auto go = [&](auto H, auto NWc) -> int {
+    FvSubgridZ<decltype(H)::value, decltype(NWc)::value> kf{
+        g, kbot, p->k_bot_full, p->nq, p->sphum - 1, p->liq_wat - 1, p->rainwat - 1, p->ice_wat - 1, p->snowwat - 1, p->graupel - 1, fra_full,
+        fra_weak, 1. / p->dt, t_max, t_min, p->rdgas, p->rvgas, p->grav, p->cp_air, p->cp_vapor, p->c_liq, p->c_ice, delp, pe, peln, pkz, delz,
+        ta, qa, ua, va, w, u_dt, v_dt, c->sg_wk};
+    static_assert(decltype(kf)::CH == 256, "grid.x above");
+    return launch_p(c, "fv_subgrid_z", grid, 0, kf);
+  };
+  auto by_nwat = [&](auto H) -> int {   // the branch set of fv_sg.F90:214-249: 0, 1, 2, 3, 4, everything else as 6
+    switch (nw) {
+      case 0: return go(H, std::integral_constant<int, 0>{});
+      case 1: return go(H, std::integral_constant<int, 1>{});
+      case 2: return go(H, std::integral_constant<int, 2>{});
+      case 3: return go(H, std::integral_constant<int, 3>{});
+      case 4: return go(H, std::integral_constant<int, 4>{});
+      default: return go(H, std::integral_constant<int, 6>{});
+    }
+  };
+  if (p->hydrostatic) RT(by_nwat(std::true_type{}));
+  else RT(by_nwat(std::false_type{}));
+  return 0;
+}
+
+extern "C" int fv3_grid_upload_dwinds(fv3_ctx *c, const fv3_grid_dwinds *h) {
+  if (!c || !h) return fail("fv3_grid_upload_dwinds: null argument");
+  if (!c->grid_ready) return fail("fv3_grid_upload_dwinds: context has no grid");
+  if (!h->vlon || !h->vlat || !h->es1 || !h->ew2 || !h->edge_vect_w || !h->edge_vect_e || !h->edge_vect_s || !h->edge_vect_n)
+    return fail("fv3_grid_upload_dwinds: null array");
+  const Grid &g = c->g;
+  const size_t r8 = 7;
+  const size_t nj = ((size_t)g.njd + r8) & ~r8, ni = ((size_t)g.nid + r8) & ~r8;
+  const size_t total = 6 * g.nA() + 3 * g.nFY() + 3 * g.nFX() + 2 * nj + 2 * ni;
+  if (!c->dw_dev) RT(rt_malloc((void **)&c->dw_dev, total * sizeof(double)));
+  double *q = c->dw_dev;
+  const double *src[8] = {h->vlon, h->vlat, h->es1, h->ew2, h->edge_vect_w, h->edge_vect_e, h->edge_vect_s, h->edge_vect_n};
+  const double **dst[8] = {&c->dw.vlon, &c->dw.vlat, &c->dw.es1, &c->dw.ew2, &c->dw.edge_vect_w, &c->dw.edge_vect_e,
+                           &c->dw.edge_vect_s, &c->dw.edge_vect_n};
+  const size_t sz[8] = {3 * g.nA(), 3 * g.nA(), 3 * g.nFY(), 3 * g.nFX(), (size_t)g.njd, (size_t)g.njd, (size_t)g.nid, (size_t)g.nid};
+  const size_t adv[8] = {3 * g.nA(), 3 * g.nA(), 3 * g.nFY(), 3 * g.nFX(), nj, nj, ni, ni};
+  for (int n = 0; n < 8; n++) {
+    RT(rtf_h2d(q, src[n], sz[n] * sizeof(double), c->stream));
+    *dst[n] = q;
+    q += adv[n];
+  }
+  RT(rtf_sync(c->stream));
+  c->dw_ready = true;
+  return 0;
+}
+
+extern "C" int fv3_update_dwinds_phys(fv3_ctx *c, double dt, const double *u_dt, const double *v_dt, double *u, double *v) {
+  FV3_ENTRY(c);
+  if (!c || !c->grid_ready) return fail("fv3_update_dwinds_phys: context has no grid");
+  if (!u_dt || !v_dt || !u || !v) return fail("fv3_update_dwinds_phys: null field");
+  const Grid &g = c->g;
+  const bool sphere = g.grid_type <= 3;   // :3338
+  if (g.grid_type == 3) return fail("fv3_update_dwinds_phys: grid_type = 3 is not built (grid_type 4 and the cubed sphere, 0..2, are)");
+  if (sphere && !c->dw_ready) return fail("fv3_update_dwinds_phys: cubed-sphere face without vlon, vlat, es, ew, edge_vect_* (fv3_grid_upload_dwinds)");
+  Dim3 grid;
+  grid.x = (unsigned)(((size_t)(g.nx + 1) * (g.ny + 1) + 255) / 256);
+  grid.y = 1;
+  grid.z = (unsigned)g.npz;
+  if (sphere) RT(launch_p(c, "update_dwinds_phys", grid, 0, UpdateDwindsPhys<true>{g, c->dw, 0.5 * dt, u_dt, v_dt, u, v}));
+  else RT(launch_p(c, "update_dwinds_phys", grid, 0, UpdateDwindsPhys<false>{g, DwindsGeom{}, 0.5 * dt, u_dt, v_dt, u, v}));
   return 0;
 }
 

@@ -676,6 +676,32 @@ class CubedSphere:
         self.da_min_c = min(float(g["area_c"][sc, sc].min()) for g in G)
         self.da_max_c = max(float(g["area_c"][sc, sc].max()) for g in G)
 
+    def _edge_vect(self, t: int) -> dict:
+        """efactor_a2c_v (fv_grid_utils.F90:942-1118): the weights with which update_dwinds_phys (and the reference's A -> C vector
+        interpolation) blends an edge value with its neighbour along the four face edges.  edge_vect_w / _e over (jsd:jed),
+        edge_vect_s / _n over (isd:ied); set on 0 .. npx, big_number elsewhere."""
+        g = self.grids[t]
+        npx, o = self.npx, self.ng - 1
+        g3, a3 = g["grid3"], g["agrid3"]
+        m2 = (npx - 1) // 2                                                        # im2 = jm2 (:988-989)
+        out = {}
+        for name, line in (("w", 1), ("e", npx), ("s", 1), ("n", npx)):
+            if name in "we":      # py(j): between the centres either side of the edge; p2(j): the mid-point of the edge segment (:994-995)
+                pc = _mid(a3[line - 1 + o, :], a3[line + o, :])
+                pm = _mid(g3[line + o, :-1], g3[line + o, 1:])
+            else:                 # px(i), p1(i) (:1056-1057)
+                pc = _mid(a3[:, line - 1 + o], a3[:, line + o])
+                pm = _mid(g3[:-1, line + o], g3[1:, line + o])
+            ev = np.full(npx - 1 + 2 * self.ng, BIG)
+            for j in range(0, npx + 1):                                            # js-1 .. je+1 (:1002-1012)
+                d1 = _gcd3(pc[j + o], pm[j + o])
+                d2 = _gcd3(pc[j + 1 + o] if j <= m2 else pc[j - 1 + o], pm[j + o])
+                ev[j + o] = d1 / (d1 + d2) if j <= m2 else d1 / (d2 + d1)
+            ev[0 + o] = ev[1 + o]                                                  # :1013-1018
+            ev[npx + o] = ev[npx - 1 + o]
+            out["edge_vect_" + name] = ev
+        return out
+
     def gridstruct(self, t: int) -> GridStruct:
         """the fv_grid_type of face t (grid_type = 0, one tile per face: all four corner flags set)"""
         if not hasattr(self, "da_min"):
@@ -715,5 +741,11 @@ class CubedSphere:
         m["ec1"], m["ec2"] = F(g["ec1"]), F(g["ec2"])
         m["en1"] = F(_unit(_cross(c0[:-1, :], c0[1:, :])))
         m["en2"] = F(_unit(_cross(c0[:, 1:], c0[:, :-1])))
+        # what update_dwinds_phys reads (fv_grid_utils.F90:3314-3326): vlon, vlat (A layout x 3); es(:,i,j,1) on (is:ie, js:je+1) and
+        # ew(:,i,j,2) on (is:ie+1, js:je), the unit vectors along the cell edges at their mid-points (:265-319); edge_vect_*
+        m["vlon"], m["vlat"] = F(vlon), F(vlat)
+        m["es1"] = F(_unit(_cross(_cross(c0[:-1, :], c0[1:, :]), _mid(c0[:-1, :], c0[1:, :]))))       # :299, :314-316
+        m["ew2"] = F(_unit(_cross(_cross(c0[:, :-1], c0[:, 1:]), _mid(c0[:, :-1], c0[:, 1:]))))       # :271, :286-288
+        m.update(self._edge_vect(t))
         gs.tile = t
         return gs

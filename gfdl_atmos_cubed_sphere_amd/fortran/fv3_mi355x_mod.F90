@@ -25,6 +25,7 @@ module fv3_mi355x_mod
   public :: FV3_CUBE_A, FV3_CUBE_B, FV3_CUBE_D, FV3_CUBE_C, FV3_CUBE_DEDGE
   public :: fv3_c2l, fv3_rayleigh_u2f, fv3_rayleigh_apply, fv3_rayleigh_super, fv3_compute_total_energy, fv3_energy_fixer_sums, fv3_remap_finish, fv3_ordered_sum, fv3_adv_pe, fv3_set_condensate, fv3_registry_mode, fv3_registry_put, fv3_registry_get, fv3_registry_host_touched, fv3_registry_fetch, fv3_registry_forget, fv3_registry_stats, fv3_set_fast_tau_w, fv3_set_ray_fast, fv3_ray_fast, fv3_mix_dp, fv3_compute_aam, fv3_consv_am_apply, fv3_set_moist, fv3_moist_params
   public :: fv3_neg_adj3, fv3_neg_adj_params
+  public :: fv3_fv_subgrid_z, fv3_sg_params, fv3_grid_dwinds, fv3_grid_upload_dwinds, fv3_update_dwinds_phys
 
   type, bind(C) :: fv3_domain
     integer(c_int) :: is, ie, js, je, ng, npx, npy, npz, grid_type
@@ -87,6 +88,20 @@ module fv3_mi355x_mod
   type, bind(C) :: fv3_neg_adj_params ! neg_adj3 (fv_sg.F90:968): the mode and the caller's constants_mod / gfdl_mp_mod values
     integer(c_int) :: hydrostatic
     real(c_double) :: rdgas, rvgas, grav, cp_air, cp_vapor, hlv, hlf, c_liq, c_ice
+  end type
+
+  type, bind(C) :: fv3_sg_params      ! fv_sg_SHiELD (fv_sg.F90:76): the mode, the tracer indices (1-based, 0 = absent), the namelist
+    integer(c_int) :: hydrostatic, nq, nwat                              ! integers and the caller's constants_mod / gfdl_mp_mod values
+    integer(c_int) :: sphum = 0, liq_wat = 0, rainwat = 0, ice_wat = 0, snowwat = 0, graupel = 0
+    integer(c_int) :: k_bot_full, fv_sg_adj, fv_sg_adj_weak = 0
+    real(c_double) :: dt, ptop
+    real(c_double) :: rdgas, rvgas, grav, cp_air, cp_vapor, c_liq, c_ice
+  end type
+
+  type, bind(C) :: fv3_grid_dwinds    ! what update_dwinds_phys reads of the gridstruct on the sphere (fv_grid_utils.F90:3314-3326):
+    type(c_ptr) :: vlon, vlat         ! host addresses; A layout x 3
+    type(c_ptr) :: es1, ew2           ! es(:,i,j,1) on (is:ie, js:je+1) x 3, ew(:,i,j,2) on (is:ie+1, js:je) x 3, component last
+    type(c_ptr) :: edge_vect_w, edge_vect_e, edge_vect_s, edge_vect_n   ! (jsd:jed), (jsd:jed), (isd:ied), (isd:ied)
   end type
 
   type, bind(C) :: fv3_remap_params   ! Lagrangian_to_Eulerian scalars (fv_mapz.F90:56-64)
@@ -642,6 +657,25 @@ module fv3_mi355x_mod
       import :: c_int, c_ptr, fv3_neg_adj_params
       type(c_ptr), value :: ctx, peln, delz, delp, pt, qv, ql, qr, qi, qs, qg, qa
       type(fv3_neg_adj_params), intent(in) :: p
+    end function
+    ! fv_sg_SHiELD (fv_sg.F90:76-505) and update_dwinds_phys (fv_grid_utils.F90:3291-3475): fv_subgrid_z of the drivers.  pe, w, delz
+    ! may be c_null_ptr in the mode that does not read them; u_dt, v_dt come back on the compute domain and are halo-updated as two
+    ! scalars by the caller before fv3_update_dwinds_phys
+    integer(c_int) function fv3_fv_subgrid_z(ctx, p, delp, pe, peln, pkz, ta, qa, ua, va, w, delz, u_dt, v_dt) &
+        bind(C, name="fv3_fv_subgrid_z")
+      import :: c_int, c_ptr, fv3_sg_params
+      type(c_ptr), value :: ctx, delp, pe, peln, pkz, ta, qa, ua, va, w, delz, u_dt, v_dt
+      type(fv3_sg_params), intent(in) :: p
+    end function
+    integer(c_int) function fv3_grid_upload_dwinds(ctx, g) bind(C, name="fv3_grid_upload_dwinds")
+      import :: c_int, c_ptr, fv3_grid_dwinds
+      type(c_ptr), value :: ctx
+      type(fv3_grid_dwinds), intent(in) :: g
+    end function
+    integer(c_int) function fv3_update_dwinds_phys(ctx, dt, u_dt, v_dt, u, v) bind(C, name="fv3_update_dwinds_phys")
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: ctx, u_dt, v_dt, u, v
+      real(c_double), value :: dt
     end function
     integer(c_int) function fv3_set_ak_bk(ctx, ak, bk) bind(C, name="fv3_set_ak_bk")
       import :: c_int, c_ptr, c_double

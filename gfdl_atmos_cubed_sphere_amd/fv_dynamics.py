@@ -9,6 +9,11 @@ theta_v / theta_m (fv_dynamics.F90:296-399, with moist_cv under use_cond / moist
 fixer and theta_v -> T in the last remap, the filter of omega (:658-662, nf_omega), neg_adj3 (:722-745, neg_adj), the angular-momentum
 fixer (:747-800, consv_am), cubed_to_latlon (:911).  Tracers that are not advected or not remapped (dnats, dnrts, :200-201, :264) and
 cld_amt's own remap order (:569-572) follow the reference.  Nudging and the diagnostics are not built.
+
+Behind ``fv_dynamics`` the drivers run ``fv_subgrid_z`` once per dt_atmos (driver/SHiELD/atmosphere.F90:599-611, driver/GFDL/
+atmosphere.F90:729-740, driver/solo/fv_phys.F90:315-354): ``fv_subgrid_z`` here is fv_sg_SHiELD and update_dwinds_phys on the device, and
+``atmosphere_step`` = ``step_from_temperature`` + ``fv_subgrid_z`` when fv_sg_adj > 0, the drivers' atmosphere_dynamics.  The rest of
+fv_update_phys (physics tendencies of T and q, the delp adjustment, nudging, del2_phys) is not built.
 """
 from __future__ import annotations
 
@@ -42,7 +47,8 @@ class FvDynamics:
                  rf_cutoff: float = 30.0e2, c2l_ord: int = 4, moist: dict | None = None, fill: bool = False, halo=None,
                  consv_te: float = 0.0, moist_phys: bool = False, radius: float = 6.3712e6, fill2d: tuple = (),
                  remap_te: bool = False, consv_am: dict | None = None, neg_adj: bool = False, check_negative: bool = False,
-                 nf_omega: int = 0, dnats: int = 0, dnrts: int = -1, cld_amt: int = 0, neg_adj_consts: dict | None = None):
+                 nf_omega: int = 0, dnats: int = 0, dnrts: int = -1, cld_amt: int = 0, neg_adj_consts: dict | None = None,
+                 fv_sg_adj: int = 0, fv_sg_adj_weak: int = 0, sg_nq: int | None = None):
         ak, bk = np.asarray(ak, dtype=np.float64), np.asarray(bk, dtype=np.float64)
         dp_ref = (ak[1:] - ak[:-1]) + (bk[1:] - bk[:-1]) * 1.0e5          # dyn_core.F90:241-244
         # flagstruct%tau / %rf_cutoff are ONE pair in the reference: Rayleigh_Friction / _Super here (fv_dynamics.F90:362-376) and Ray_fast /
@@ -83,6 +89,13 @@ class FvDynamics:
         # the tracer indices (1-based) of the six species: the moist dict's, by default the first six in the reference's usual order
         self.neg_adj_species = tuple(int((moist or {}).get(n, k + 1))
                                      for k, n in enumerate(("sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel")))
+        # fv_subgrid_z: flagstruct%fv_sg_adj / %fv_sg_adj_weak (seconds, integers; <= 0: off), sg_nq = the leading tracers that are mixed
+        # (nt_dyn of the SHiELD / GFDL drivers, min(6, nq) of fv_phys.F90:346; default: all).  k_bot_full is flags.n_sponge.
+        if not 0 <= (nq if sg_nq is None else sg_nq) <= nq:
+            raise ValueError(f"FvDynamics: sg_nq = {sg_nq} must lie in 0..nq = {nq}")
+        self.fv_sg_adj, self.fv_sg_adj_weak, self.sg_nq = int(fv_sg_adj), int(fv_sg_adj_weak), int(nq if sg_nq is None else sg_nq)
+        self.sg_nwat = int((moist or {}).get("nwat", 0))
+        self.sg_species = {n: int((moist or {}).get(n, 0)) for n in ("sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel")}
         self.rank = rank
         self.negative_report = []          # check_negative: (when, name, minimum) of what fell below its threshold
         # fill2D (fv_dynamics.F90:542-556, FILL2D builds): the 0-based tracer indices of liq_wat, rainwat, ice_wat, snowwat, graupel
@@ -160,6 +173,33 @@ class FvDynamics:
         if self.consv_am:                                                  # :747-800
             self._consv_am(bdt)
         self.cubed_to_latlon()                                             # :911
+
+    # -- fv_subgrid_z ---------------------------------------------------------------------------------------------
+    def fv_subgrid_z(self, bdt: float):
+        """fv_sg_SHiELD and the update of the D-grid winds with the tendencies it returns (driver/SHiELD/atmosphere.F90:587-611,
+        fv_update_phys.F90:620-626, :735): on the state step_from_temperature leaves (pt = T, ua / va, pkz, pe, peln)."""
+        d, ctx, fl = self.dc.d, self.ctx, self.fl
+        if self.fv_sg_adj <= 0:
+            raise ValueError("FvDynamics.fv_subgrid_z: fv_sg_adj <= 0 (the drivers do not call fv_sg_SHiELD then)")
+        if not self.sg_nq:
+            raise ValueError("FvDynamics.fv_subgrid_z: no tracer to mix (fv_sg_SHiELD reads q(:,:,:,sphum))")
+        hyd = fl.hydrostatic
+        npz = ctx.npz
+        if "u_dt" not in d:
+            d["u_dt"], d["v_dt"] = ctx.zeros("A", npz), ctx.zeros("A", npz)
+        d["u_dt"].zero()                                                   # atmosphere.F90:587-588
+        d["v_dt"].zero()
+        ctx.fv_subgrid_z(hyd, self.sg_nq, self.sg_nwat, self.sg_species, fl.n_sponge, self.fv_sg_adj, self.fv_sg_adj_weak, bdt, fl.ptop,
+                         d["delp"], d["pe"] if hyd else None, d["peln"], d["pkz"], d["pt"], d["q"], d["ua"], d["va"],
+                         None if hyd else d["w"], None if hyd else d["delz"], d["u_dt"], d["v_dt"], consts=self.neg_adj_consts)
+        self.dc.halo.update([(d["u_dt"], "A"), (d["v_dt"], "A")])          # fv_update_phys.F90:620-626: two scalars
+        ctx.update_dwinds_phys(bdt, d["u_dt"], d["v_dt"], d["u"], d["v"])  # :735
+
+    def atmosphere_step(self, bdt: float):
+        """the drivers' atmosphere_dynamics: fv_dynamics, then fv_subgrid_z when fv_sg_adj > 0"""
+        self.step_from_temperature(bdt)
+        if self.fv_sg_adj > 0:
+            self.fv_subgrid_z(bdt)
 
     # -- neg_adj3 -------------------------------------------------------------------------------------------------
     def _prt_negative(self, when: str):

@@ -36,7 +36,8 @@ EXPORTS = ["fv3_last_error", "fv3_create", "fv3_destroy", "fv3_set_stream", "fv3
            "fv3_halo_unpack", "fv3_pt_to_theta_v", "fv3_c2l", "fv3_rayleigh_u2f", "fv3_rayleigh_apply", "fv3_rayleigh_super", "fv3_compute_total_energy", "fv3_energy_fixer_sums", "fv3_remap_finish", "fv3_ordered_sum", "fv3_adv_pe", "fv3_omga_update", "fv3_divg2_ext", "fv3_one_grad_p", "fv3_one_grad_p_nh", "fv3_copy_a_to_cc", "fv3_heat_source_accum", "fv3_del2_cubed", "fv3_apply_heat_source", "fv3_profile", "fv3_profile_report", "fv3_comm_get_unique_id", "fv3_comm_init", "fv3_comm_destroy", "fv3_halo_start", "fv3_halo_complete", "fv3_allreduce_max", "fv3_cube_table", "fv3_cube_halo_start", "fv3_cube_halo_complete",
            "fv3_set_dp_ref", "fv3_update_dz_c", "fv3_set_condensate", "fv3_set_fast_tau_w", "fv3_set_ray_fast", "fv3_ray_fast", "fv3_mix_dp", "fv3_compute_aam", "fv3_consv_am_apply", "fv3_riem_solver_c", "fv3_update_dz_d", "fv3_riem_solver3",
            "fv3_p_grad_c", "fv3_nh_p_grad", "fv3_split_p_grad", "fv3_grad1_p_update", "fv3_d_sw_inline_q", "fv3_flux_accum", "fv3_fill2d_mass", "fv3_fill2d_apply", "fv3_set_remap_te", "fv3_profile_report_timers", "fv3_prt_maxmin", "fv3_pk3_halo", "fv3_pe_halo", "fv3_geopk", "fv3_zh_from_delz", "fv3_set_ak_bk", "fv3_set_moist", "fv3_lagrangian_to_eulerian",
-           "fv3_tracer_2d_prep", "fv3_tracer_2d_scale", "fv3_tracer_2d_step", "fv3_neg_adj3"]
+           "fv3_tracer_2d_prep", "fv3_tracer_2d_scale", "fv3_tracer_2d_step", "fv3_neg_adj3",
+           "fv3_fv_subgrid_z", "fv3_grid_upload_dwinds", "fv3_update_dwinds_phys"]
 
 
 class Fv3Error(RuntimeError):
@@ -148,6 +149,20 @@ class _RemapParams(C.Structure):
 class _NegAdjParams(C.Structure):
     _fields_ = [("hydrostatic", C.c_int)] + [(n, C.c_double) for n in ["rdgas", "rvgas", "grav", "cp_air", "cp_vapor", "hlv", "hlf",
                                                                         "c_liq", "c_ice"]]
+
+
+class _SgParams(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ["hydrostatic", "nq", "nwat", "sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel",
+                                       "k_bot_full", "fv_sg_adj", "fv_sg_adj_weak"]] + [
+        (n, C.c_double) for n in ["dt", "ptop", "rdgas", "rvgas", "grav", "cp_air", "cp_vapor", "c_liq", "c_ice"]]
+
+
+SG_SPECIES = ("sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel")
+_DWINDS = ("vlon", "vlat", "es1", "ew2", "edge_vect_w", "edge_vect_e", "edge_vect_s", "edge_vect_n")
+
+
+class _GridDwinds(C.Structure):
+    _fields_ = [(n, _dp) for n in _DWINDS]
 
 
 class _MoistParams(C.Structure):
@@ -424,6 +439,45 @@ class Context:
                                                  vc.p, ua.p, va.p, divg_d.p, mfx.p, mfy.p, cx.p, cy.p, crx.p, cry.p,
                                                  xfx.p, yfx.p, _pp(q_con), delp_out.p, pt_out.p, u_out.p, v_out.p,
                                                  _pp(w_out), _pp(q_con_out), _pp(heat_s), _pp(diss_e)), fn)
+
+    def fv_subgrid_z(self, hydrostatic, nq, nwat, species, k_bot_full, fv_sg_adj, fv_sg_adj_weak, dt, ptop, delp, pe, peln, pkz, ta, qa,
+                     ua, va, w, delz, u_dt, v_dt, consts=None):
+        """fv_sg_SHiELD (model/fv_sg.F90:76-505) in place on ta, qa(.., 1:nq), ua, va, w; the A-grid wind tendencies into u_dt, v_dt.
+        species: {name: 1-based index} of sphum, liq_wat, rainwat, ice_wat, snowwat, graupel (absent = 0); consts: overrides of
+        NEG_ADJ_CONSTS (the caller's constants_mod / gfdl_mp_mod values)."""
+        pr = _SgParams()
+        pr.hydrostatic, pr.nq, pr.nwat = int(bool(hydrostatic)), int(nq), int(nwat)
+        for n in SG_SPECIES:
+            setattr(pr, n, int((species or {}).get(n, 0)))
+        pr.k_bot_full, pr.fv_sg_adj, pr.fv_sg_adj_weak = int(k_bot_full), int(fv_sg_adj), int(fv_sg_adj_weak)
+        pr.dt, pr.ptop = float(dt), float(ptop)
+        cs = dict(NEG_ADJ_CONSTS, **(consts or {}))
+        for n in ("rdgas", "rvgas", "grav", "cp_air", "cp_vapor", "c_liq", "c_ice"):
+            setattr(pr, n, float(cs[n]))
+        self.lib.check(self.lib.dll.fv3_fv_subgrid_z(self.h, C.byref(pr), _pp(delp), _pp(pe), _pp(peln), _pp(pkz), _pp(ta), _pp(qa),
+                                                     _pp(ua), _pp(va), _pp(w), _pp(delz), _pp(u_dt), _pp(v_dt)), "fv3_fv_subgrid_z")
+
+    def upload_dwinds(self, m=None):
+        """fv3_grid_upload_dwinds: vlon, vlat, es1, ew2, edge_vect_* of the gridstruct (or of the mapping m) -- what
+        update_dwinds_phys reads on the sphere.  Once per context."""
+        m = self.grid.m if m is None else m
+        gd, keep = _GridDwinds(), []
+        for n in _DWINDS:
+            if n not in m:
+                raise Fv3Error(f"upload_dwinds: the gridstruct has no {n}")
+            a = np.asfortranarray(m[n], dtype=np.float64)
+            keep.append(a)
+            setattr(gd, n, a.ctypes.data_as(_dp))
+        self.lib.check(self.lib.dll.fv3_grid_upload_dwinds(self.h, C.byref(gd)), "fv3_grid_upload_dwinds")
+        self.dwinds_ready = True
+
+    def update_dwinds_phys(self, dt, u_dt, v_dt, u, v):
+        """update_dwinds_phys (model/fv_grid_utils.F90:3291-3475): u, v += the A-grid tendencies u_dt, v_dt (halo updated) on the D grid.
+        On the sphere the geometry is uploaded on first use."""
+        if self.grid.grid_type < 3 and not getattr(self, "dwinds_ready", False):
+            self.upload_dwinds()
+        self.lib.check(self.lib.dll.fv3_update_dwinds_phys(self.h, C.c_double(dt), _pp(u_dt), _pp(v_dt), _pp(u), _pp(v)),
+                       "fv3_update_dwinds_phys")
 
     def profile(self, enable: bool):
         self.lib.check(self.lib.dll.fv3_profile(self.h, C.c_int(int(enable))), "fv3_profile")

@@ -646,6 +646,63 @@ typedef struct fv3_neg_adj_params {
 int fv3_neg_adj3(fv3_ctx *ctx, const fv3_neg_adj_params *p, const double *peln, const double *delz, const double *delp,
                  double *pt, double *qv, double *ql, double *qr, double *qi, double *qs, double *qg, double *qa);
 
+/* fv_subgrid_z -- what every driver of the reference runs once per dt_atmos right after fv_dynamics (driver/SHiELD/atmosphere.F90:
+ * 599-611, driver/GFDL/atmosphere.F90:729-740, driver/solo/fv_phys.F90:315-354): fv_sg_SHiELD, then the A-grid wind tendencies it
+ * returns carried to the D-grid winds by update_dwinds_phys (fv_update_phys.F90:620-626, :673, :735).  The sequence of a caller:
+ * zero u_dt, v_dt; fv3_fv_subgrid_z; halo update of u_dt, v_dt as two scalars; fv3_update_dwinds_phys.
+ *
+ * fv3_fv_subgrid_z -- fv_sg_SHiELD, model/fv_sg.F90:76-505: three bottom-to-top sweeps (ratio 0.25, 0.5, 0.999, :263-271) with a
+ * Richardson-number test per layer pair (:315-342), the mass-weighted exchange of the tracers, u, v, w and energy (:343-386; the
+ * enthalpy difference is mixed into the total energy, :378-380, as the reference does), the temperature back from the energy
+ * hydrostatically or at constant volume with the moist heat capacities of nwat (:392-451), and the relaxation by fra(k) (:456-478).
+ * kbot and fra(k): :123-128, :161-169 (fra = dt / fv_sg_adj down to k_bot_full, dt / fv_sg_adj_weak below it where that is > 0;
+ * kbot = k_bot_full unless fv_sg_adj_weak > 0, then npz).  t_min (:129-133) is 160 where ptop < 2 Pa, else 165: the reference
+ * reads pe(is,1,js) on the host, so the caller hands ptop.  t_max (:135-139) is 315 where k_bot_full < min(npz, 24), else 325.
+ * nwat: 0, 1, 2, 3, 4 take the branches the reference has for them; every other value takes its `else` branches (:242-248, :302-307,
+ * :358-361, :436-442), which read all five condensates: 6, and likewise 5, 7, ... when the five indices are given.
+ * The 1-based tracer indices are those get_tracer_index returns (:141-153); 0 = absent.  Needed: sphum unless nwat = 0; liq_wat
+ * for nwat >= 2; rainwat for nwat >= 4; ice_wat for nwat = 3 and >= 5; snowwat, graupel for nwat >= 5.  nq: the leading tracers
+ * of qa that are mixed (nt_dyn of the SHiELD / GFDL drivers, min(6, nq) of fv_phys.F90:346).
+ * delp, ta, ua, va, w, u_dt, v_dt: A x npz; qa: A x npz x (at least nq); pkz, delz: CC x npz; pe (is-1:ie+1, npz+1, js-1:je+1)
+ * (hydrostatic only, else it may be NULL); peln (is:ie, npz+1, js:je) (both modes: pm, :194); w, delz may be NULL when hydrostatic.
+ * Written, in place, on the compute domain and levels 1..kbot: ta, qa(.., 1:nq), ua, va, w (unless hydrostatic), u_dt, v_dt.
+ * Nothing else: halos, levels below kbot and tracers beyond nq keep their bits.
+ * Refused (status 1 and a message, nothing launched): null fields; fv_sg_adj <= 0; k_bot_full < 1; k_bot_full > npz with
+ * fv_sg_adj_weak <= 0 (the reference would overrun its column arrays); a species index outside 1..nq that nwat needs; nwat < 0.
+ * The columns' working copies (fv_sg.F90:102-103) are a work array of (7 + nq) x kbot x nx x ny doubles ((5 + nq) when hydrostatic)
+ * that the context keeps until fv3_destroy and grows when a call needs more: 2.1 GB for a 384 x 384 x 127 tile at full depth with
+ * nq = 7, 0.5 GB at k_bot_full = 30. */
+typedef struct fv3_sg_params {
+  int hydrostatic, nq, nwat;
+  int sphum, liq_wat, rainwat, ice_wat, snowwat, graupel;   /* 1-based, 0 = absent */
+  int k_bot_full, fv_sg_adj, fv_sg_adj_weak;                /* integers, as in the reference (:83-84, :92) */
+  double dt, ptop;
+  double rdgas, rvgas, grav, cp_air, cp_vapor, c_liq, c_ice;  /* the caller's constants_mod / gfdl_mp values */
+} fv3_sg_params;
+int fv3_fv_subgrid_z(fv3_ctx *ctx, const fv3_sg_params *p, const double *delp, const double *pe, const double *peln,
+                     const double *pkz, double *ta, double *qa, double *ua, double *va, double *w, const double *delz,
+                     double *u_dt, double *v_dt);
+
+/* What update_dwinds_phys reads of the gridstruct on the sphere (model/fv_grid_utils.F90:3314-3326), component-last planes like ec1
+ * of fv3_grid_cubed: vlon, vlat (unit_vect_latlon of agrid, :2220-2243; A layout x 3), es1 = es(:,i,j,1) on (is:ie, js:je+1) x 3
+ * (:293-319), ew2 = ew(:,i,j,2) on (is:ie+1, js:je) x 3 (:265-291), edge_vect_w / _e (jsd:jed) and edge_vect_s / _n (isd:ied)
+ * (efactor_a2c_v, :942-1118).  HOST pointers, copied once; call after fv3_grid_upload.  Not needed for grid_type = 4. */
+typedef struct fv3_grid_dwinds {
+  const double *vlon, *vlat;
+  const double *es1, *ew2;
+  const double *edge_vect_w, *edge_vect_e, *edge_vect_s, *edge_vect_n;
+} fv3_grid_dwinds;
+int fv3_grid_upload_dwinds(fv3_ctx *ctx, const fv3_grid_dwinds *g);
+
+/* update_dwinds_phys -- model/fv_grid_utils.F90:3291-3475, call sites fv_update_phys.F90:620-626, :673, :735: the A-grid wind
+ * tendencies u_dt, v_dt (A x npz, one ring of halo read, which the caller has updated as two scalars) added to the D-grid winds
+ * u (U x npz, i = is..ie, j = js..je+1) and v (V x npz, i = is..ie+1, j = js..je), in place.  grid_type = 4: the two-point average
+ * (:3338-3349).  grid_type 0..2: the 3-D tendency vector through vlon / vlat (:3353-3359), the sums to the cell edges (:3362-3376),
+ * the edge_vect_* blend on the four face edges (:3378-3455) and the projection on es(:,:,:,1) / ew(:,:,:,2) (:3456-3469); refused
+ * without fv3_grid_upload_dwinds.  Not built: grid_type = 3, update2d_dwinds_phys (dwind_2d, :3478), regional and nested domains
+ * (bounded_domain: the edge blend is switched off there). */
+int fv3_update_dwinds_phys(fv3_ctx *ctx, double dt, const double *u_dt, const double *v_dt, double *u, double *v);
+
 /* Per-kernel timing with HIP events recorded on the context's stream around every kernel the
  * library launches (this is what bench.py's roofline figures are measured with).  report: one line
  * "label count total_ms" per kernel label since the last report; synchronises the stream. */
