@@ -35,38 +35,8 @@ struct DswCubedState {
 };
 
 // D1a: contravariant winds, first layer: the interior form where it applies and the edge rows / columns that follow from
-// uc, vc alone (:671-690, :695-701, :711-717, :731-737, :748-754); box (isd:ied+1, jsd:jed+1)
-struct DswCubedD1a {
-  DswCubedState s;
-  FV3_HD void operator()(int i, int j, int k) const {
-    const Grid &g = s.g;
-    const int npx = g.npx, npy = g.npy;
-    const CA uc = cview_V(g, s.a.uc), vc = cview_U(g, s.a.vc);
-    const double dt = s.a.dt;
-    if (j <= g.jed && i >= g.is - 1 && i <= g.ie + 2) {
-      const VA ut = view_V(g, s.ut);
-      if (i == 1 || i == npx) {
-        const double u0 = uc(i, j, k);
-        ut(i, j, k) = (u0 * dt > 0.) ? u0 / g.sinsg(i - 1, j, 3) : u0 / g.sinsg(i, j, 1);
-      } else if (j != 0 && j != 1 && j != npy - 1 && j != npy) {
-        ut(i, j, k) = (uc(i, j, k) - 0.25 * g.cosa_u[g.iV(i, j)] * (vc(i - 1, j, k) + vc(i, j, k) + vc(i - 1, j + 1, k) + vc(i, j + 1, k))) *
-                      g.rsin_u[g.iV(i, j)];
-      }
-    }
-    if (i <= g.ied && j >= g.js - 1 && j <= g.je + 2) {
-      const VA vt = view_U(g, s.vt);
-      if (j == 1 || j == npy) {
-        const double v0 = vc(i, j, k);
-        vt(i, j, k) = (v0 * dt > 0.) ? v0 / g.sinsg(i, j - 1, 4) : v0 / g.sinsg(i, j, 2);
-      } else {
-        vt(i, j, k) = (vc(i, j, k) - 0.25 * g.cosa_v[g.iU(i, j)] * (uc(i, j - 1, k) + uc(i + 1, j - 1, k) + uc(i, j, k) + uc(i + 1, j, k))) *
-                      g.rsin_v[g.iU(i, j)];
-      }
-    }
-  }
-};
-
-// D1a as a tile kernel whose threads MARCH: 64 lanes along i, four groups of kRows consecutive rows; the rows of uc / vc a thread has read
+// uc, vc alone (:671-690, :695-701, :711-717, :731-737, :748-754); box (isd:ied+1, jsd:jed+1).
+// A tile kernel whose threads MARCH: 64 lanes along i, four groups of kRows consecutive rows; the rows of uc / vc a thread has read
 // serve two rows of results (ut(j) reads vc(j), vc(j+1); vt(j) reads uc(j-1), uc(j)), so a point costs 4 field loads and 4 metric loads
 // instead of 10 + 4.  What D1a waits for is its loads' way through the L1 (profiles/r06_pmc_pass.csv: 90 M cache-line accesses a launch,
 // 18 per 8-byte-a-lane load instruction, for 0.76 GB of HBM traffic).  The statements and their conditions are D1a's: the same bits.

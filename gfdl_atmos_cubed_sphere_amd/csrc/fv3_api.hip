@@ -47,108 +47,110 @@ using namespace fv3;
 #endif
 
 struct CubePlanDev;
+// rows per wavefront segment of the marching kernels (c_sw's: by geometry mode, csw_march)
+constexpr int kMarchTj = 48;
 struct fv3_ctx {
-  fv3_domain dom;
-  Grid g;           // device view (pointers into dev_metrics)
-  stream_t stream;
+  fv3_domain dom = {};
+  Grid g = {};      // device view (pointers into dev_metrics)
+  stream_t stream = {};
   // side stream: the few levels that take the LDS-tile kernels in d_sw (sponge layers) run concurrently with
   // the marching kernels of the other levels (different levels = disjoint data)
-  stream_t stream2;
-  void *ev_fork, *ev_join;
+  stream_t stream2 = {};
+  void *ev_fork = nullptr, *ev_join = nullptr;
   // lanes (dsw_cubed, csw_cubed): lane 1 = launches go to stream2 -- the frame / sponge-level passes of a cubed-sphere face beside the
   // marching kernels of its interior.  ev_mid: a second main -> side dependency inside one routine.  A face group keeps the side
   // stream and the events on its first member.
   int lane = 0;
   void *ev_mid = nullptr;
-  bool side_ok;          // transport and momentum route the same levels to the tile kernels
+  bool side_ok = false;  // transport and momentum route the same levels to the tile kernels
   // the two ways of dividing the levels between the marching and the LDS-tile kernels of d_sw: [0] strict (no damping branch in the
   // marching kernels), [1] with the sponge levels of the reference defaults (nord_k = 0, nord_w = 0: dsw_fused.h run_bf) on the marching
   // side -- the active one (klist, n_plain, ...) is chosen per d_sw call (lev_activate)
   struct LevSel { int *klist, *klist_m; int n_plain, n_damp, n_plain_m, n_rest_m; bool side_ok; } lev_sel[2] = {};
-  int use_side;          // FV3_MI355X_SIDE_STREAM=0 disables
-  int sponge_march;      // FV3_MI355X_SPONGE_MARCH=0: the sponge levels stay on the LDS-tile kernels
-  int round_simds;       // SIMDs of the device (CUs x 4): x wavefronts per SIMD of a kernel = the wavefronts resident at once
+  int use_side = 1;      // FV3_MI355X_SIDE_STREAM=0 disables
+  int sponge_march = 1;  // FV3_MI355X_SPONGE_MARCH=0: the sponge levels stay on the LDS-tile kernels
+  int round_simds = 0;   // SIMDs of the device (CUs x 4): x wavefronts per SIMD of a kernel = the wavefronts resident at once
                          // (balance_segments); FV3_MI355X_ROUND_SIMDS overrides, 0 = no balancing
-  double *dev_metrics;   // one allocation holding every metric array
-  bool grid_ready;
+  double *dev_metrics = nullptr;   // one allocation holding every metric array
+  bool grid_ready = false;
   // per-level d_sw coefficients on the device
-  int *lev_i;      // 4*npz
-  double *lev_d;   // 5*npz
-  bool lev_ready;
+  int *lev_i = nullptr;      // 4*npz
+  double *lev_d = nullptr;   // 5*npz
+  bool lev_ready = false;
   // optional per-kernel timing with HIP events on the launch stream (fv3_profile / fv3_profile_report)
   // nonhydrostatic path: dp_ref + edge_profile coefficients, scratch slabs (A x (npz+1) each)
-  double *dp0;        // device, npz
-  double *edge_dev;   // device, 4*npz: gk, bet, gam, 1 / bet; then EdgeProfileLds::kTabDoubles: the rows' table (nh_fast.h edge_rows)
-  EdgeCoef ec;
-  bool dp0_ready;
-  double *scratch[8];
-  double *ray_d;         // pm(k), rf(k) of Rayleigh_Friction
+  double *dp0 = nullptr;        // device, npz
+  double *edge_dev = nullptr;   // device, 4*npz: gk, bet, gam, 1 / bet; then EdgeProfileLds::kTabDoubles: the rows' table (nh_fast.h edge_rows)
+  EdgeCoef ec = {};
+  bool dp0_ready = false;
+  double *scratch[8] = {};
+  double *ray_d = nullptr;         // pm(k), rf(k) of Rayleigh_Friction
   // host-address field registry (fv3_registry_*): host array -> its device mirror and which of the two copies is current
   struct RegEntry { const void *host; void *dev; size_t bytes; bool dev_current, host_current; };
-  std::vector<RegEntry> *reg;
-  int reg_lazy;
-  long long reg_stat[4];   // h2d copies, h2d skipped, d2h copies, d2h deferred
-  double *rff_d;         // rff(k) of fast_tau_w_sec (npz, 1.0 below k_rf) or null; rf(k), dp(k) of Ray_fast behind it (fv3_set_ray_fast)
-  int rff_on, rayf_kmax, rayf_krf;
-  double rayf_dm;
-  bool moist_on;         // fv3_set_moist: moist thermodynamics of the remap
-  bool remap_te_on;      // fv3_set_remap_te: total energy remapped in the place of T_v / theta_v
-  const double *rte_hs;  // A
-  double *rte_te;        // A x npz work array
-  fv3_moist_params moist;
-  double *moist_qcon, *moist_cappa;
-  const double *q_con, *cappa;  // fv3_set_condensate: use_cond / moist_kappa arrays of the Riemann solvers (or null)
-  double *remap_scr;     // coordinate + profile slabs of the vertical remap (fv3_lagrangian_to_eulerian)
-  size_t remap_scr_n;
-  double *lev_ext_d;  // damp(npz+1) for update_dz_d
-  int *lev_ext_i;     // ndif(npz+1)
-  double *trc_d;      // device, 2*npz: cmax, frac
-  int *trc_i;         // device, npz: ksplt
-  double *akbk;       // device, 2*(npz+1)
-  int *kord_tr_dev;   // device, up to 64 tracers
-  bool akbk_ready;
+  std::vector<RegEntry> *reg = nullptr;
+  int reg_lazy = 0;
+  long long reg_stat[4] = {};   // h2d copies, h2d skipped, d2h copies, d2h deferred
+  double *rff_d = nullptr;      // rff(k) of fast_tau_w_sec (npz, 1.0 below k_rf) or null; rf(k), dp(k) of Ray_fast behind it (fv3_set_ray_fast)
+  int rff_on = 0, rayf_kmax = -1, rayf_krf = 0;
+  double rayf_dm = 1.;
+  bool moist_on = false;         // fv3_set_moist: moist thermodynamics of the remap
+  bool remap_te_on = false;      // fv3_set_remap_te: total energy remapped in the place of T_v / theta_v
+  const double *rte_hs = nullptr;  // A
+  double *rte_te = nullptr;        // A x npz work array
+  fv3_moist_params moist = {};
+  double *moist_qcon = nullptr, *moist_cappa = nullptr;
+  const double *q_con = nullptr, *cappa = nullptr;  // fv3_set_condensate: use_cond / moist_kappa arrays of the Riemann solvers (or null)
+  double *remap_scr = nullptr;     // coordinate + profile slabs of the vertical remap (fv3_lagrangian_to_eulerian)
+  size_t remap_scr_n = 0;
+  double *lev_ext_d = nullptr;  // damp(npz+1) for update_dz_d
+  int *lev_ext_i = nullptr;     // ndif(npz+1)
+  double *trc_d = nullptr;      // device, 2*npz: cmax, frac
+  int *trc_i = nullptr;         // device, npz: ksplt
+  double *akbk = nullptr;       // device, 2*(npz+1)
+  int *kord_tr_dev = nullptr;   // device, up to 64 tracers
+  bool akbk_ready = false;
   // levels with del-2n damping of delp / w / pt go to the LDS-tile transport kernel, the others march
-  int *klist;            // device, npz: [plain levels..., damped levels...]
-  int n_plain, n_damp;
+  int *klist = nullptr;            // device, npz: [plain levels..., damped levels...]
+  int n_plain = 0, n_damp = 0;
   // same split for the momentum part: marching needs nord_k == 1, no vorticity damping, d_con = 0
-  int *klist_m;
-  int n_plain_m, n_rest_m;
-  int *klist_z;          // npz+1 interfaces of update_dz_d: [undamped..., damped...]
-  int n_plain_z, n_damp_z;
+  int *klist_m = nullptr;
+  int n_plain_m = 0, n_rest_m = 0;
+  int *klist_z = nullptr;          // npz+1 interfaces of update_dz_d: [undamped..., damped...]
+  int n_plain_z = 0, n_damp_z = 0;
   // peer exchange (fv3_comm_*, fv3_halo_start / _complete): RCCL communicator, its stream, events, message buffers
-  void *comm;
-  int comm_rank, comm_size;
-  stream_t comm_stream;
-  void *ev_packed, *ev_arrived;
-  double *msg_send[8], *msg_recv[8];
-  size_t msg_cap[8];
-  int pend_n;
+  void *comm = nullptr;
+  int comm_rank = 0, comm_size = 1;
+  stream_t comm_stream = {};
+  void *ev_packed = nullptr, *ev_arrived = nullptr;
+  double *msg_send[8] = {}, *msg_recv[8] = {};
+  size_t msg_cap[8] = {};
+  int pend_n = 0;
   // cube-edge exchange (fv3_cube_halo_start / _complete): per-kind pack / unpack plans of this face, message buffers, pending group
-  struct CubePlanDev *cube_plan[5];
-  int cube_face;
-  double *cube_send, *cube_recv;
-  size_t cube_cap_send, cube_cap_recv;
-  int cube_pend_n;
-  fv3_cube_field cube_pend[FV3_HALO_MAX_FIELDS];
-  size_t cube_roff[FV3_HALO_MAX_FIELDS][6];
-  fv3_halo_field pend_fields[FV3_HALO_MAX_FIELDS];
-  int col_pool;      // workgroups of the pooled launches of the column solvers (0: one workgroup per 256 columns)
-  int cubed_frame;   // cubed-sphere hybrid: width of the frame the pass kernels own (0: passes on the whole face)
-  int cubed_reach;   // ... and how much wider the frame of the passes' intermediates is
-  int cubed_frame_c; // the frame of c_sw (d2a2c_vect has its edge forms within 4 points of an edge)
-  int lev_max_nord;      // max over the levels of nord_k
-  int lev_max_nord_v, lev_max_nord_w, lev_max_nord_t;   // ... of nord_v / nord_w / nord_t over the levels where the damping is on
-  bool lev_has_damp_v4, lev_has_damp_v5, lev_has_damp_t;  // damp_vt > 1e-4 (deln of delp) / > 1e-5 (del6 of vorticity); damp_t > 1e-4
-  bool lev_has_dcon;     // some level has d_con_k > 1e-5
-  bool lev_has_vt_damp, lev_has_w_damp, lev_has_w_damp_hi;  // damp_vt / damp_t; damp_w > 1e-5; the latter with nord_w > 0
-  double *ke_scr;        // B kind, npz levels: KE + damping term at the corners
-  double *mflux[2];      // mass-flux scratch of the marching transports: FX kind, FY kind (npz levels)
-  double *heat_scr[2];   // heat_s / diss_e of a d_sw call whose caller passed NULL and whose levels are not all on the branch-free kernels
+  struct CubePlanDev *cube_plan[5] = {};
+  int cube_face = -1;
+  double *cube_send = nullptr, *cube_recv = nullptr;
+  size_t cube_cap_send = 0, cube_cap_recv = 0;
+  int cube_pend_n = 0;
+  fv3_cube_field cube_pend[FV3_HALO_MAX_FIELDS] = {};
+  size_t cube_roff[FV3_HALO_MAX_FIELDS][6] = {};
+  fv3_halo_field pend_fields[FV3_HALO_MAX_FIELDS] = {};
+  int col_pool = 0;      // workgroups of the pooled launches of the column solvers (0: one workgroup per 256 columns)
+  int cubed_frame = 4;   // cubed-sphere hybrid: width of the frame the pass kernels own (0: passes on the whole face)
+  int cubed_reach = 5;   // ... and how much wider the frame of the passes' intermediates is
+  int cubed_frame_c = 7; // the frame of c_sw (d2a2c_vect has its edge forms within 4 points of an edge)
+  int lev_max_nord = 0;      // max over the levels of nord_k
+  int lev_max_nord_v = 0, lev_max_nord_w = 0, lev_max_nord_t = 0;   // ... of nord_v / nord_w / nord_t over the levels where the damping is on
+  bool lev_has_damp_v4 = false, lev_has_damp_v5 = false, lev_has_damp_t = false;  // damp_vt > 1e-4 (deln of delp) / > 1e-5 (del6 of vorticity); damp_t > 1e-4
+  bool lev_has_dcon = false;     // some level has d_con_k > 1e-5
+  bool lev_has_vt_damp = false, lev_has_w_damp = false, lev_has_w_damp_hi = false;  // damp_vt / damp_t; damp_w > 1e-5; the latter with nord_w > 0
+  double *ke_scr = nullptr;      // B kind, npz levels: KE + damping term at the corners
+  double *mflux[2] = {};         // mass-flux scratch of the marching transports: FX kind, FY kind (npz levels)
+  double *heat_scr[2] = {};      // heat_s / diss_e of a d_sw call whose caller passed NULL and whose levels are not all on the branch-free kernels
   // cubed sphere (grid_type < 3): edge weights / corner factors and the work arrays of the pass kernels (B x (npz+1) each)
-  CubedGeom cg;
-  double *cg_dev;
-  double *cs_scr[36];
-  int *ones_i;    // npz ones, device (ksplt of the inline_q sub-step)
+  CubedGeom cg = {};
+  double *cg_dev = nullptr;
+  double *cs_scr[36] = {};
+  int *ones_i = nullptr;    // npz ones, device (ksplt of the inline_q sub-step)
   // fv_subgrid_z (subgrid_z.h): the columns' working copies of fv3_fv_subgrid_z, and what update_dwinds_phys reads of the gridstruct
   // on the sphere (fv3_grid_upload_dwinds)
   double *sg_wk = nullptr;
@@ -158,23 +160,21 @@ struct fv3_ctx {
   bool dw_ready = false;
   std::vector<double> host_area;   // prt_maxmin: area on the host, and g_sum's global_area
   double global_area = 0.;
-  int march_tj;          // rows per wavefront segment of the marching kernels
-  int march_tj_csw, march_tj_ke, march_tj_fused, march_tj_mom;
-  int trc_nt;  // tracers per wavefront in the sub-cycle kernel (FV3_MI355X_TRACER_NT: 1..4, default 3)
-  int remap_nt;  // tracers per thread in the remap (FV3_MI355X_REMAP_NT: 1..3, default 3)
-  int riem_blocked;   // the same for the Riemann solvers' four slabs (FV3_MI355X_RIEM_SCR: 0 / 1, default 1)
-  int pgrad_fused;    // nh_p_grad as ONE kernel where the domain has no face edges (NhPGradFused; FV3_MI355X_PGRAD_FUSED=0: a2b_ord4 + the gradient)
-  int riem_lds;       // the dry SIM1 Riemann solvers with the levels across the lanes, BIT-IDENTICAL to the slab kernels (nh_fast.h
-                      // RiemFast<CG, true>; FV3_MI355X_RIEM_LDS: 0 / 1, default 1)
-  int remap_blocked;  // scratch slabs of the remap in per-wavefront blocks (FV3_MI355X_REMAP_SCR: 0 / 1, default 1)
-  int remap_lds;      // the remap with the column in LDS (remap_fast.h; bit-identical to the slab kernels) where it is built for the
-                      // configuration (FV3_MI355X_REMAP_LDS: 0 / 1, default 1)
-  int tj_fixed;          // an FV3_MI355X_MARCH_TJ* variable is set: take the rows per segment as given
-  int tj_env_fused;      // ... one of the d_sw kernels' (FV3_MI355X_MARCH_TJ_FUSED / _MOM)
-  int csw_kpw;           // levels per wavefront in CswMarch (1 or 2; FV3_MI355X_CSW_KPW)
-  int use_fused;         // 1: delp + w + pt in one marching kernel when the schemes allow (FV3_MI355X_FUSED=0: off)
-  int use_march;         // 0: LDS-tile kernels only (FV3_MI355X_MARCH=0)
-  bool prof_on;
+  int march_tj_fused = kMarchTj;   // rows per segment of the fused d_sw kernels, transports and momentum (FV3_MI355X_MARCH_TJ_FUSED)
+  int trc_nt = 3;  // tracers per wavefront in the sub-cycle kernel (FV3_MI355X_TRACER_NT: 1..4, default 3)
+  int remap_nt = 3;  // tracers per thread in the remap (FV3_MI355X_REMAP_NT: 1..3, default 3)
+  int riem_blocked = 1;   // the same for the Riemann solvers' four slabs (FV3_MI355X_RIEM_SCR: 0 / 1, default 1)
+  int pgrad_fused = 1;    // nh_p_grad as ONE kernel where the domain has no face edges (NhPGradFused; FV3_MI355X_PGRAD_FUSED=0: a2b_ord4 + the gradient)
+  int riem_lds = 1;       // the dry SIM1 Riemann solvers with the levels across the lanes, BIT-IDENTICAL to the slab kernels (nh_fast.h
+                          // RiemFast<CG, true>; FV3_MI355X_RIEM_LDS: 0 / 1, default 1)
+  int remap_blocked = 1;  // scratch slabs of the remap in per-wavefront blocks (FV3_MI355X_REMAP_SCR: 0 / 1, default 1)
+  int remap_lds = 1;      // the remap with the column in LDS (remap_fast.h; bit-identical to the slab kernels) where it is built for the
+                          // configuration (FV3_MI355X_REMAP_LDS: 0 / 1, default 1)
+  int tj_fixed = 0;          // FV3_MI355X_MARCH_TJ_FUSED is set: take the rows per segment as given (seg_rows)
+  int tj_env_fused = 0;      // ... and no 55-row rule for the interior of a cubed-sphere face
+  int use_fused = 1;         // 1: delp + w + pt in one marching kernel when the schemes allow (FV3_MI355X_FUSED=0: off)
+  int use_march = 1;         // 0: LDS-tile kernels only (FV3_MI355X_MARCH=0)
+  bool prof_on = false;
   struct ProfRec { const char *label; void *e0, *e1; };
   std::vector<ProfRec> prof;
   struct fv3_group *grp = nullptr;   // the faces one rank holds, launched together (fv3_group_create)
@@ -376,8 +376,7 @@ static int lane_prepare(fv3_ctx *c) {
   // (a stream of its own for the lanes, of low priority: the marching kernels of the main stream are the critical path, the passes fill
   // what they leave; the periodic path's stream2 has the same role)
   if (!o->stream2) {
-    static const int low = [] { const char *e = std::getenv("FV3_MI355X_SIDE_PRIO"); return e ? std::atoi(e) : 1; }();   // 0: normal priority
-    if (int rc = low ? rt_stream_create_low(&o->stream2) : rt_stream_create(&o->stream2)) return rc;
+    if (int rc = rt_stream_create_low(&o->stream2)) return rc;
   }
   if (!o->ev_fork) { if (int rc = rt_event_create(&o->ev_fork)) return rc; }
   if (!o->ev_join) { if (int rc = rt_event_create(&o->ev_join)) return rc; }
@@ -402,71 +401,36 @@ static int rtf_sync(stream_t st) { if (int rc = grp_flush_all()) return rc; retu
 static int rtf_event_record(void *e, stream_t st) { if (int rc = grp_flush_all()) return rc; rt_event_record(e, st); return 0; }
 static int rtf_stream_wait_event(stream_t st, void *e) { if (int rc = grp_flush_all()) return rc; rt_stream_wait_event(st, e); return 0; }
 
-// launch + optional event pair around it
-template <class F>
-static int launch_p(fv3_ctx *c, const char *label, Dim3 grid, size_t lds_doubles, const F &f) {
-  if (c->grp) return grp_defer<F, 0>(c, label, grid, lds_doubles, 0, f);
+// launch + optional event pair around it.  KIND (and W, the column kernels' wavefronts per SIMD) as in grp_defer / launch_group:
+// 0 launch, 1 launch_2w, 2 launch_cols (a = lanes), 3 launch_waves (a = wavefronts).  In a face group the launch is queued.
+template <int KIND, int W = 0, class F>
+static int launch_any(fv3_ctx *c, const char *label, Dim3 grid, size_t lds_doubles, int a, const F &f) {
+  if (c->grp) return grp_defer<F, KIND, W>(c, label, grid, lds_doubles, a, f);
+  const stream_t s = lane_stream(c);
   void *e0 = nullptr, *e1 = nullptr;
   if (c->prof_on) {
     if (prof_events(&e0, &e1)) return 1;
-    rt_event_record(e0, lane_stream(c));
+    rt_event_record(e0, s);
   }
-  int rc = launch(grid, lds_doubles, lane_stream(c), f);
+  int rc;
+  if constexpr (KIND == 0) rc = launch(grid, lds_doubles, s, f);
+  else if constexpr (KIND == 1) rc = launch_2w(grid, lds_doubles, s, f);
+  else if constexpr (KIND == 2) rc = launch_cols<W>(grid, s, f, a);
+  else rc = launch_waves(a, s, f);
   if (c->prof_on) {
-    rt_event_record(e1, lane_stream(c));
+    rt_event_record(e1, s);
     c->prof.push_back({label, e0, e1});
   }
   return rc;
 }
-
 template <class F>
-static int launch_p2(fv3_ctx *c, const char *label, Dim3 grid, size_t lds_doubles, const F &f) {
-  if (c->grp) return grp_defer<F, 1>(c, label, grid, lds_doubles, 0, f);
-  void *e0 = nullptr, *e1 = nullptr;
-  if (c->prof_on) {
-    if (prof_events(&e0, &e1)) return 1;
-    rt_event_record(e0, lane_stream(c));
-  }
-  int rc = launch_2w(grid, lds_doubles, lane_stream(c), f);
-  if (c->prof_on) {
-    rt_event_record(e1, lane_stream(c));
-    c->prof.push_back({label, e0, e1});
-  }
-  return rc;
-}
-
+static int launch_p(fv3_ctx *c, const char *label, Dim3 grid, size_t lds_doubles, const F &f) { return launch_any<0>(c, label, grid, lds_doubles, 0, f); }
+template <class F>
+static int launch_p2(fv3_ctx *c, const char *label, Dim3 grid, size_t lds_doubles, const F &f) { return launch_any<1>(c, label, grid, lds_doubles, 0, f); }
 template <int W = 0, class F>
-static int launch_c(fv3_ctx *c, const char *label, Dim3 grid, const F &f, int lanes = 0) {
-  if (c->grp) return grp_defer<F, 2, W>(c, label, grid, 0, lanes, f);
-  void *e0 = nullptr, *e1 = nullptr;
-  if (c->prof_on) {
-    if (prof_events(&e0, &e1)) return 1;
-    rt_event_record(e0, lane_stream(c));
-  }
-  int rc = launch_cols<W>(grid, lane_stream(c), f, lanes);
-  if (c->prof_on) {
-    rt_event_record(e1, lane_stream(c));
-    c->prof.push_back({label, e0, e1});
-  }
-  return rc;
-}
-
+static int launch_c(fv3_ctx *c, const char *label, Dim3 grid, const F &f, int lanes = 0) { return launch_any<2, W>(c, label, grid, 0, lanes, f); }
 template <class F>
-static int launch_w(fv3_ctx *c, const char *label, int nwaves, const F &f) {
-  if (c->grp) return grp_defer<F, 3>(c, label, Dim3{0, 0, 0}, 0, nwaves, f);
-  void *e0 = nullptr, *e1 = nullptr;
-  if (c->prof_on) {
-    if (prof_events(&e0, &e1)) return 1;
-    rt_event_record(e0, lane_stream(c));
-  }
-  int rc = launch_waves(nwaves, lane_stream(c), f);
-  if (c->prof_on) {
-    rt_event_record(e1, lane_stream(c));
-    c->prof.push_back({label, e0, e1});
-  }
-  return rc;
-}
-
+static int launch_w(fv3_ctx *c, const char *label, int nwaves, const F &f) { return launch_any<3>(c, label, Dim3{0, 0, 0}, 0, nwaves, f); }
 
 // ---- FV3_MI355X_POISON: the memory contract of the work arrays (debug switch; docs/SWITCHES.md) -----------------------------------
 // The work arrays (cs_scr, scratch, mflux, ke_scr, heat_scr, remap_scr, the message buffers) are allocated once and shared between
@@ -636,6 +600,42 @@ static int profile_report_impl(fv3_ctx *c, char *out, size_t cap, bool timers) {
 extern "C" int fv3_profile_report(fv3_ctx *c, char *out, size_t cap) { return profile_report_impl(c, out, cap, false); }
 extern "C" int fv3_profile_report_timers(fv3_ctx *c, char *out, size_t cap) { return profile_report_impl(c, out, cap, true); }
 
+// The switches a context reads when it is created (docs/SWITCHES.md), each with its clamp.  The others are read
+// once per process where they are used (function-local statics on env_int).
+static void ctx_switches(fv3_ctx *c) {
+  c->use_march = env_int("FV3_MI355X_MARCH", 1);
+  c->use_fused = env_int("FV3_MI355X_FUSED", 1);
+  c->use_side = env_int("FV3_MI355X_SIDE_STREAM", 1);
+  c->sponge_march = env_int("FV3_MI355X_SPONGE_MARCH", 1);
+  c->poison = env_int("FV3_MI355X_POISON", 0) != 0;
+#ifndef FV3_HOST_EMU
+  int dev = 0, ncu = 0;
+  if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+    c->round_simds = 4 * ncu;
+#endif
+  c->round_simds = env_int("FV3_MI355X_ROUND_SIMDS", c->round_simds);
+  // 48 rows (eight segments of a 384-row tile): measured on one set of arrays with all 127 levels on the marching kernels -- 0.773 ms
+  // against 0.794 for seven segments of 55 rows trimmed to whole rounds and 0.786 / 0.780 for ten / nine (tools/pair_ab2.py).  Set: the
+  // rows per segment of every marching kernel are taken as given, no balancing to whole rounds of the chip (seg_rows)
+  bool tj_set = false;
+  c->march_tj_fused = env_int("FV3_MI355X_MARCH_TJ_FUSED", kMarchTj, &tj_set); if (c->march_tj_fused < 1) c->march_tj_fused = kMarchTj;
+  c->tj_fixed = c->tj_env_fused = tj_set;
+  c->trc_nt = env_int("FV3_MI355X_TRACER_NT", 3); if (c->trc_nt < 1 || c->trc_nt > 4) c->trc_nt = 3;
+  c->remap_nt = env_int("FV3_MI355X_REMAP_NT", 3); if (c->remap_nt < 1 || c->remap_nt > RemapFields::kGroupMax) c->remap_nt = 3;
+  c->riem_blocked = env_int("FV3_MI355X_RIEM_SCR", 1) != 0;
+  c->remap_blocked = env_int("FV3_MI355X_REMAP_SCR", 1) != 0;
+  c->col_pool = env_int("FV3_MI355X_COL_POOL", 0); if (c->col_pool < 0) c->col_pool = 0;
+  c->pgrad_fused = env_int("FV3_MI355X_PGRAD_FUSED", 1) != 0;
+  c->riem_lds = env_int("FV3_MI355X_RIEM_LDS", 1) != 0;
+  c->remap_lds = env_int("FV3_MI355X_REMAP_LDS", 1);   // 0: slab kernels, 1: the LDS kernels where they pay (fv3_lagrangian_to_eulerian), 2: wherever built
+  // the levels-across-the-lanes kernels index the fields with 32 bits (nh_fast.h ix_t): a tile whose fields reach 2^32 bytes takes the
+  // slab kernels (1030 x 1030 x 128 is 1.1e9 bytes)
+  if ((size_t)c->g.nB() * (size_t)(c->g.npz + 2) >= ((size_t)1 << 29)) c->riem_lds = c->remap_lds = 0;
+  c->cubed_frame = env_int("FV3_MI355X_CUBED_FRAME", 4); if (c->cubed_frame < 0) c->cubed_frame = 0;
+  c->cubed_frame_c = env_int("FV3_MI355X_CUBED_FRAME_C", c->cubed_frame ? 7 : 0); if (c->cubed_frame_c < 0) c->cubed_frame_c = 0;
+  c->cubed_reach = env_int("FV3_MI355X_CUBED_REACH", 5); if (c->cubed_reach < 1) c->cubed_reach = 5;
+}
+
 extern "C" int fv3_create(const fv3_domain *dom, fv3_ctx **out) {
   if (!dom || !out) return fail("fv3_create: null argument");
   if (dom->ng != NG) return fail("fv3_create: ng must be %d", NG);
@@ -649,7 +649,6 @@ extern "C" int fv3_create(const fv3_domain *dom, fv3_ctx **out) {
   if (!c) return fail("fv3_create: out of host memory");
   c->dom = *dom;
   Grid &g = c->g;
-  std::memset(&g, 0, sizeof g);
   g.is = dom->is; g.ie = dom->ie; g.js = dom->js; g.je = dom->je;
   g.isd = dom->is - NG; g.ied = dom->ie + NG; g.jsd = dom->js - NG; g.jed = dom->je + NG;
   g.npx = dom->npx; g.npy = dom->npy; g.npz = dom->npz;
@@ -658,117 +657,7 @@ extern "C" int fv3_create(const fv3_domain *dom, fv3_ctx **out) {
   g.do_diss_est = dom->do_diss_est; g.prevent_diss_cooling = dom->prevent_diss_cooling;
   g.stretched_grid = dom->stretched_grid;
   g.lim_fac = dom->lim_fac;
-  c->stream = nullptr;
-  c->stream2 = nullptr; c->ev_fork = c->ev_join = nullptr; c->side_ok = false;
-  c->dev_metrics = nullptr;
-  c->grid_ready = false;
-  c->lev_i = nullptr; c->lev_d = nullptr; c->lev_ready = false;
-  c->prof_on = false;
-  c->klist = nullptr; c->n_plain = c->n_damp = 0;
-  c->klist_m = nullptr; c->n_plain_m = c->n_rest_m = 0; c->ke_scr = nullptr;
-  c->klist_z = nullptr; c->n_plain_z = c->n_damp_z = 0;
-  c->mflux[0] = c->mflux[1] = nullptr;
-  c->heat_scr[0] = c->heat_scr[1] = nullptr;
-  std::memset(&c->cg, 0, sizeof c->cg);
-  c->cg_dev = nullptr;
-  for (auto &p : c->cs_scr) p = nullptr;
-  c->comm = nullptr; c->comm_rank = 0; c->comm_size = 1; c->comm_stream = nullptr; c->ev_packed = c->ev_arrived = nullptr;
-  for (int d = 0; d < 8; d++) { c->msg_send[d] = c->msg_recv[d] = nullptr; c->msg_cap[d] = 0; }
-  c->pend_n = 0;
-  for (int n = 0; n < 5; n++) c->cube_plan[n] = nullptr;
-  c->cube_face = -1; c->cube_send = c->cube_recv = nullptr; c->cube_cap_send = c->cube_cap_recv = 0; c->cube_pend_n = 0;
-  {  // tuning / fallback knobs
-    const char *e = std::getenv("FV3_MI355X_MARCH");
-    c->use_march = e ? std::atoi(e) : 1;
-    e = std::getenv("FV3_MI355X_SIDE_STREAM");
-    c->use_side = e ? std::atoi(e) : 1;
-    e = std::getenv("FV3_MI355X_POISON");
-    c->poison = (e && std::atoi(e) != 0) ? 1 : 0;
-    e = std::getenv("FV3_MI355X_SPONGE_MARCH");
-    c->sponge_march = e ? std::atoi(e) : 1;
-    c->round_simds = 0;
-#ifndef FV3_HOST_EMU
-    {
-      int dev = 0, ncu = 0;
-      if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-        c->round_simds = 4 * ncu;
-    }
-#endif
-    e = std::getenv("FV3_MI355X_ROUND_SIMDS");
-    if (e) c->round_simds = std::atoi(e);
-    c->tj_fixed = 0;
-    for (const char *v : {"FV3_MI355X_MARCH_TJ", "FV3_MI355X_MARCH_TJ_FUSED", "FV3_MI355X_MARCH_TJ_MOM",
-                          "FV3_MI355X_MARCH_TJ_KE", "FV3_MI355X_MARCH_TJ_CSW"})
-      if (std::getenv(v)) c->tj_fixed = 1;
-    c->tj_env_fused = (std::getenv("FV3_MI355X_MARCH_TJ_FUSED") || std::getenv("FV3_MI355X_MARCH_TJ_MOM")) ? 1 : 0;
-    e = std::getenv("FV3_MI355X_MARCH_TJ");
-    c->march_tj = e ? std::atoi(e) : 48;
-    if (c->march_tj < 1) c->march_tj = 48;
-    e = std::getenv("FV3_MI355X_CSW_KPW");
-    c->csw_kpw = e ? std::atoi(e) : 0;   // 0 = by geometry mode (fv3_c_sw)
-    if (c->csw_kpw < 0 || c->csw_kpw > 2) c->csw_kpw = 0;   // (three and four levels per wavefront were measured in round 1 and never won)
-    e = std::getenv("FV3_MI355X_FUSED");
-    c->use_fused = e ? std::atoi(e) : 1;
-    e = std::getenv("FV3_MI355X_MARCH_TJ_FUSED");
-    // 48 rows (eight segments of a 384-row tile): measured on one set of arrays with all 127 levels on the marching kernels -- 0.773 ms
-    // against 0.794 for seven segments of 55 rows trimmed to whole rounds and 0.786 / 0.780 for ten / nine (tools/pair_ab2.py)
-    c->march_tj_fused = e ? std::atoi(e) : 48;
-    if (c->march_tj_fused < 1) c->march_tj_fused = 48;
-    e = std::getenv("FV3_MI355X_MARCH_TJ_MOM");
-    c->march_tj_mom = e ? std::atoi(e) : c->march_tj_fused;
-    if (c->march_tj_mom < 1) c->march_tj_mom = c->march_tj_fused;
-    e = std::getenv("FV3_MI355X_TRACER_NT");
-    c->trc_nt = e ? std::atoi(e) : 3;
-    if (c->trc_nt < 1 || c->trc_nt > 4) c->trc_nt = 3;
-    e = std::getenv("FV3_MI355X_REMAP_NT");
-    c->remap_nt = e ? std::atoi(e) : 3;
-    if (c->remap_nt < 1 || c->remap_nt > RemapFields::kGroupMax) c->remap_nt = 3;
-    e = std::getenv("FV3_MI355X_RIEM_SCR");
-    c->riem_blocked = e ? (std::atoi(e) != 0) : 1;
-    e = std::getenv("FV3_MI355X_RIEM_LDS");
-    c->riem_lds = e ? (std::atoi(e) != 0) : 1;
-    const char *ef = std::getenv("FV3_MI355X_PGRAD_FUSED");
-    c->pgrad_fused = ef ? (std::atoi(ef) != 0) : 1;
-    e = std::getenv("FV3_MI355X_REMAP_SCR");
-    c->remap_blocked = e ? (std::atoi(e) != 0) : 1;
-    e = std::getenv("FV3_MI355X_REMAP_LDS");
-    c->remap_lds = e ? std::atoi(e) : 1;   // 0: slab kernels, 1: the LDS kernels where they pay (fv3_lagrangian_to_eulerian), 2: wherever built
-    // the levels-across-the-lanes kernels index the fields with 32 bits (nh_fast.h ix_t): a tile whose fields reach 2^32 bytes takes the
-    // slab kernels (1030 x 1030 x 128 is 1.1e9 bytes)
-    if ((size_t)g.nB() * (size_t)(g.npz + 2) >= ((size_t)1 << 29)) {
-      c->riem_lds = 0;
-      c->remap_lds = 0;
-    }
-    e = std::getenv("FV3_MI355X_MARCH_TJ_KE");
-    c->march_tj_ke = e ? std::atoi(e) : 48;
-    if (c->march_tj_ke < 1) c->march_tj_ke = 48;
-    e = std::getenv("FV3_MI355X_COL_POOL");
-    c->col_pool = e ? std::atoi(e) : 0;
-    if (c->col_pool < 0) c->col_pool = 0;
-    e = std::getenv("FV3_MI355X_CUBED_FRAME");
-    c->cubed_frame = e ? std::atoi(e) : 4;
-    if (c->cubed_frame < 0) c->cubed_frame = 0;
-    e = std::getenv("FV3_MI355X_CUBED_FRAME_C");
-    c->cubed_frame_c = e ? std::atoi(e) : (c->cubed_frame ? 7 : 0);
-    if (c->cubed_frame_c < 0) c->cubed_frame_c = 0;
-    e = std::getenv("FV3_MI355X_CUBED_REACH");
-    c->cubed_reach = e ? std::atoi(e) : 5;
-    if (c->cubed_reach < 1) c->cubed_reach = 5;
-    e = std::getenv("FV3_MI355X_MARCH_TJ_CSW");
-    c->march_tj_csw = e ? std::atoi(e) : 0;   // 0 = by geometry mode (fv3_c_sw)
-    if (c->march_tj_csw < 0) c->march_tj_csw = 0;
-  }
-  c->dp0 = nullptr; c->edge_dev = nullptr; c->dp0_ready = false;
-  c->akbk = nullptr; c->kord_tr_dev = nullptr; c->akbk_ready = false;
-  c->remap_scr = nullptr; c->remap_scr_n = 0; c->ray_d = nullptr;
-  c->reg = nullptr; c->reg_lazy = 0; c->reg_stat[0] = c->reg_stat[1] = c->reg_stat[2] = c->reg_stat[3] = 0;
-  c->rff_d = nullptr; c->rff_on = 0; c->rayf_kmax = -1; c->rayf_krf = 0; c->rayf_dm = 1.;
-  c->q_con = nullptr; c->cappa = nullptr;
-  c->moist_on = false; c->moist_qcon = nullptr; c->moist_cappa = nullptr;
-  c->remap_te_on = false; c->rte_hs = nullptr; c->rte_te = nullptr;
-  c->trc_d = nullptr; c->trc_i = nullptr; c->ones_i = nullptr;
-  for (auto &s : c->scratch) s = nullptr;
-  c->lev_ext_d = nullptr; c->lev_ext_i = nullptr;
+  ctx_switches(c);
   *out = c;
   return 0;
 }
@@ -881,45 +770,14 @@ extern "C" int fv3_group_destroy(fv3_group *g) {
   return rc ? fail("fv3_group_destroy: a queued launch failed") : 0;
 }
 
-// Field arrays come back from hipMalloc aligned to 2 MB, i.e. every field starts at the same phase of the HBM channel interleave; a
-// stencil kernel that streams six or ten fields at the same (i, j, k) then sends all its streams to the same channels at the same
-// time.  FV3_MI355X_MALLOC_SKEW=S (bytes, a multiple of 256; default below) starts the n-th array n * S bytes (mod 64 KB) into its
-// allocation, so the streams of a kernel sit at different phases.  0: as hipMalloc returns them.
-static std::unordered_map<void *, void *> g_skewed;   // user pointer -> allocation
-static size_t malloc_skew() {
-  static const size_t v = [] {
-    const char *e = std::getenv("FV3_MI355X_MALLOC_SKEW");
-    long n = e ? std::atol(e) : 0;
-    if (n < 0) n = 0;
-    return (size_t)(n / 256 * 256);
-  }();
-  return v;
-}
+// (Field arrays come back from hipMalloc aligned to 2 MB, every field at the same phase of the HBM channel interleave.  Offsetting the
+// allocations against each other was measured and is not the default: the arrays are as hipMalloc returns them.)
 extern "C" int fv3_malloc(void **dptr, size_t bytes) {
-#ifndef FV3_HOST_EMU
-  const size_t sk = malloc_skew();
-  if (sk && bytes >= (1u << 20)) {
-    static size_t counter = 0;
-    const size_t off = (counter++ * sk) % 65536;
-    void *base = nullptr;
-    RT(rt_malloc(&base, bytes + 65536));
-    *dptr = static_cast<char *>(base) + off;
-    g_skewed[*dptr] = base;
-    return 0;
-  }
-#endif
   RT(rt_malloc(dptr, bytes));
   return 0;
 }
 extern "C" int fv3_free(void *dptr) {
   RT(grp_flush_all());   // a queued launch of a face group may still use the buffer
-  auto it = g_skewed.find(dptr);
-  if (it != g_skewed.end()) {
-    void *base = it->second;
-    g_skewed.erase(it);
-    RT(rt_free(base));
-    return 0;
-  }
   RT(rt_free(dptr));
   return 0;
 }
@@ -1088,7 +946,7 @@ extern "C" int fv3_grid_upload(fv3_ctx *c, const fv3_grid_host *h) {
       uniform = uniform && all_eq(u.src, u.n, u.src[0]);
     }
     g.geom = uniform ? 2 : (ortho ? 1 : 0);
-    if (const char *e = std::getenv("FV3_MI355X_GEOM")) g.geom = std::min(g.geom, std::max(0, std::atoi(e)));
+    g.geom = std::min(g.geom, std::max(0, env_int("FV3_MI355X_GEOM", g.geom)));
   }
   RT(rtf_sync(c->stream));  // host buffers may go away after the call returns
   c->grid_ready = true;
@@ -1270,12 +1128,7 @@ struct Tp2dKernel {
 template <class F>
 static int launch_box(fv3_ctx *c, const char *label, int i0, int i1, int j0, int j1, int nk, const F &f) {
   if (i1 < i0 || j1 < j0 || nk <= 0) return 0;
-  static const int rows_env = [] {
-    const char *e = std::getenv("FV3_MI355X_BOX_ROWS");
-    const int n = e ? std::atoi(e) : 16;
-    return (n == 4 || n == 8 || n == 16) ? n : 16;
-  }();
-  const int rows = (j1 - j0 + 1 >= 64) ? rows_env : 4;
+  const int rows = (j1 - j0 + 1 >= 64) ? 16 : 4;
   Dim3 grid;
   grid.x = (unsigned)((i1 - i0 + 64) / 64);
   grid.y = (unsigned)((j1 - j0 + rows) / rows);
@@ -1313,12 +1166,52 @@ static int launch_pass(fv3_ctx *c, const char *label, int i0, int i1, int j0, in
   grid.z = (unsigned)rg.nk;
   return launch_p(c, label, grid, 0, kf);
 }
-// n-th work array of the cubed-sphere kernels: (nid+1) x (njd+1) x (npz+1) doubles, allocated on first use
+// The work arrays of the cubed-sphere kernels, fv3_ctx::cs_scr: (nid+1) x (njd+1) x (npz+1) doubles each, allocated on first use.
+//
+//   slots     taken by                                   as
+//   0 .. 3    c_sw (csw_cubed)                           its four intermediates
+//   0 .. 7    a2b_ord4 (run_a2b)                         qx, qy of up to four fields: 0 / 1, 2 / 3, ...
+//   0, 1      d_sw, Smagorinsky coefficient              qx, qy of its a2b_ord4 -- c_sw's, free while d_sw runs
+//   4 .. 7    fv_tp_2d (tp2d_cubed)                      fx2, fy2, q_i, q_j
+//   4 .. 6    deln_flux: fv3_fv_tp_2d, d_sw, tracer_2d   d2, fx2, fy2 -- scratch 4 .. 6 of fv_tp_2d, free between its calls
+//   8 .. 20   d_sw (dsw_cubed)                           ut, vt, fx, fy, gxw, gyw, gx, gy, ke, wk, dd, svc, suc
+//   8 .. 13   c_sw, two lanes                            the passes' copies of ua, va, uc, vc, ut, vt -- d_sw's, free while c_sw runs
+//   8, 9      update_dz_d, tracer_2d                     fx, fy of the field in hand -- d_sw's, free outside it
+//   10, 11    update_dz_d, del6_vt_flux of zh            fx2, fy2 (with d2 = 4)
+//   21 .. 28  d_sw, each where the call needs it         vortv; dfx2, dfy2; smag; wfx2, wfy2; gxq, gyq
+//   29 .. 32  d_sw, FV3_MI355X_LANE_D2=1                 the frame's own crx, cry, xfx, yfx
+//   29        d_sw_inline_q                              the mean mass of pt's damping -- after d_sw has returned
+//   30        lagrangian_to_eulerian, remap_te           u before the remap -- outside d_sw
+//   33        d_sw, del6_vt_flux of the vorticity        d2 of its own: the chain may run beside the transports' (4) on the side lane
+//
+// The numbers are the order the arrays came to be; they stay, because the order of first allocation decides the addresses.
+enum CsSlot {
+  kCsCsw = 0, kCsA2b = 0,
+  kCsTpFx2 = 4, kCsTpFy2, kCsTpQi, kCsTpQj,
+  kCsDelnD2 = 4, kCsDelnFx2, kCsDelnFy2,
+  kCsDsw = 8, kCsCswLane = 8, kCsFx = 8, kCsFy, kCsZhFx2, kCsZhFy2,
+  kCsVortv = 21, kCsDfx2, kCsDfy2, kCsSmag, kCsWfx2, kCsWfy2, kCsGxq, kCsGyq,
+  kCsLaneD2 = 29, kCsInlineQMass = 29, kCsRemapUOld = 30,
+  kCsVortD2 = 33,
+};
 static double *cs_scratch(fv3_ctx *c, int n) {
   if (!c->cs_scr[n]) {
     if (work_alloc(c, "cs_scr", n, &c->cs_scr[n], c->g.nB() * (size_t)(c->g.npz + 1))) return nullptr;
   }
   return c->cs_scr[n];
+}
+// the slots a routine takes, in this order: *out = the array, or `who`'s failure
+struct CsWant { int slot; double **out; };
+static int cs_take(fv3_ctx *c, const char *who, std::initializer_list<CsWant> want) {
+  for (const CsWant &w : want)
+    if (!(*w.out = cs_scratch(c, w.slot))) return fail("%s: out of device memory", who);
+  return 0;
+}
+// ... n consecutive slots from `first`
+static int cs_take_n(fv3_ctx *c, const char *who, int first, int n, double **const *out) {
+  for (int m = 0; m < n; m++)
+    if (int rc = cs_take(c, who, {{first + m, out[m]}})) return rc;
+  return 0;
 }
 static bool is_cubed(const fv3_ctx *c) { return c->g.grid_type < 3; }
 
@@ -1380,9 +1273,7 @@ static int tp2d_cubed(fv3_ctx *c, int nk, const double *q, const double *crx, co
   Tp2dCubedState s;
   s.g = g; s.q = q; s.crx = crx; s.cry = cry; s.xfx = xfx; s.yfx = yfx; s.ra_x = ra_x; s.ra_y = ra_y;
   s.mfx = mfx; s.mfy = mfy; s.fx = fx; s.fy = fy; s.hord = hord;
-  double **scr[4] = {&s.fx2, &s.fy2, &s.q_i, &s.q_j};
-  for (int n = 0; n < 4; n++)
-    if (!(*scr[n] = cs_scratch(c, 4 + n))) return fail("fv_tp_2d: out of device memory");
+  if (cs_take(c, "fv_tp_2d", {{kCsTpFx2, &s.fx2}, {kCsTpFy2, &s.fy2}, {kCsTpQi, &s.q_i}, {kCsTpQj, &s.q_j}})) return 1;
   // Frame launches (rg.w = the consumer's frame wo + cubed_reach): the consumers (D4, D9, the zh / tracer updates) read the fluxes of
   // the faces of their own cells, i.e. within wo + 1 of an edge; an outer-sweep face reads q_i / q_j three cells further (wo + 4),
   // q_i / q_j the inner fluxes one face further (wo + 5).  Each pass runs on the frame it is read on, not on the widest one.
@@ -1398,7 +1289,7 @@ static int tp2d_cubed(fv3_ctx *c, int nk, const double *q, const double *crx, co
 }
 
 // the same on the frame of width w3 (flux points) for up to three fields in one launch (cubed_tpf.h); fields[0] is weighted with
-// xfx / yfx, the following ones with fields[0]'s fluxes; FV3_MI355X_FRAME_FUSED=0 falls back to the passes
+// xfx / yfx, the following ones with fields[0]'s fluxes
 static int tp2d_frame_fused(fv3_ctx *c, const TpfField *fields, int nf, const double *crx, const double *cry, const double *xfx,
                             const double *yfx, int w3, const int *klist, int nk, const char *label, bool full = false,
                             const double *emfx = nullptr, const double *emfy = nullptr, const double *dfx = nullptr,
@@ -1425,24 +1316,11 @@ static int tp2d_frame_fused(fv3_ctx *c, const TpfField *fields, int nf, const do
   return launch_p(c, label, grid, (size_t)kTfArrays * kTfMaxN, kf);
 }
 static bool deln_fused_on() {
-  static const int v = [] {
-    const char *e = std::getenv("FV3_MI355X_DELN_FUSED");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int v = env_int("FV3_MI355X_DELN_FUSED", 1);
   return v != 0;
 }
 static bool flux_march_on() {
-  static const int v = [] {
-    const char *e = std::getenv("FV3_MI355X_FLUX_MARCH");
-    return e ? std::atoi(e) : 1;
-  }();
-  return v != 0;
-}
-static bool frame_fused_on() {
-  static const int v = [] {
-    const char *e = std::getenv("FV3_MI355X_FRAME_FUSED");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int v = env_int("FV3_MI355X_FLUX_MARCH", 1);
   return v != 0;
 }
 
@@ -1450,8 +1328,8 @@ static int csw_march(fv3_ctx *c, const CswArgs &ca);
 static int csw_cubed(fv3_ctx *c, const CswArgs &ca) {
   const Grid &g = c->g;
   double *scr[4];
-  for (int n = 0; n < 4; n++)
-    if (!(scr[n] = cs_scratch(c, n))) return fail("c_sw: out of device memory");
+  double **scr_p[4] = {&scr[0], &scr[1], &scr[2], &scr[3]};
+  if (cs_take_n(c, "c_sw", kCsCsw, 4, scr_p)) return 1;
   CswCubedState s = make_csw_cubed(g, ca, scr);
   const int npz = g.npz;
   // Hybrid (see dsw_cubed): d2a2c_vect switches to its edge forms within npt = 4 points of a face edge, so the frame the
@@ -1469,8 +1347,7 @@ static int csw_cubed(fv3_ctx *c, const CswArgs &ca) {
   const bool lanes = hyb && lanes_pay(c);
   if (lanes) {
     double **wk[6] = {&s.ua_w, &s.va_w, &s.uc_w, &s.vc_w, &s.ut_w, &s.vt_w};
-    for (int n = 0; n < 6; n++)
-      if (!(*wk[n] = cs_scratch(c, 8 + n))) return fail("c_sw: out of device memory");
+    if (cs_take_n(c, "c_sw", kCsCswLane, 6, wk)) return 1;
     s.own_w = wo;
     RT(lane_prepare(c));
     RT(lane_op(c, kLaneFork));
@@ -1544,8 +1421,7 @@ extern "C" int fv3_fv_tp_2d(fv3_ctx *c, int nk, const double *q, const double *c
       DelnCubedState d;
       d.g = g; d.q = q; d.mass = mfx ? mass : nullptr; d.fx = fx; d.fy = fy; d.nord = c->trc_i + g.npz; d.coef = c->trc_d + 2 * g.npz; d.thresh = 1.E-4;
       d.corner_area = 0;
-      d.d2 = cs_scratch(c, 4); d.fx2 = cs_scratch(c, 5); d.fy2 = cs_scratch(c, 6);
-      if (!d.d2 || !d.fx2 || !d.fy2) return fail("fv3_fv_tp_2d: out of device memory");
+      if (cs_take(c, "fv3_fv_tp_2d", {{kCsDelnD2, &d.d2}, {kCsDelnFx2, &d.fx2}, {kCsDelnFy2, &d.fy2}})) return 1;
       const PassRegion r{0, nullptr, nk};
       RT(launch_pass(c, "fv_tp_2d", g.isd, g.ied, g.jsd, g.jed, r, DelnCubedL1{d}));
       RT(launch_pass(c, "fv_tp_2d", g.isd, g.ied + 1, g.jsd, g.jed + 1, r, DelnCubedL24{d, 1, 0}));
@@ -1620,7 +1496,7 @@ extern "C" int fv3_ppm_line(fv3_ctx *c, int iord, int which, const double *h, co
 // serial march, not throughput).  Never below 8 rows (the 6 warm-up rows of every segment are overhead).
 // FV3_MI355X_DEBUG_SEGMENTS=1: the segmentation every marching launch of the pair ended up with, on stderr
 static void seg_report(const char *who, const MarchDims &d, int nlev) {
-  static const int on = [] { const char *e = std::getenv("FV3_MI355X_DEBUG_SEGMENTS"); return e ? std::atoi(e) : 0; }();
+  static const int on = env_int("FV3_MI355X_DEBUG_SEGMENTS", 0);
   if (on)
     std::fprintf(stderr, "[fv3 segments] %s: %d level slots x %d strips x %d segments of %d rows; %d of the slots (spread evenly): %d segments of %d rows\n", who, nlev,
                  d.nstrips, d.nsegs, d.tj, d.alt_nk, d.alt_ng, d.alt_tj);
@@ -1674,12 +1550,13 @@ static int csw_march(fv3_ctx *c, const CswArgs &ca) {
   {
     // rows per segment: 64 for the two-levels-per-wavefront kernel (one wavefront per SIMD); the uniform-metric kernel
     // (one level per wavefront, four per SIMD, bandwidth-bound) does better with many short segments (measured 16-40: 24)
-    const int tj_csw = c->march_tj_csw ? c->march_tj_csw : (c->g.geom == 2 ? 24 : 64);
-    MarchDims md = make_csw_dims(c->g, seg_rows(c, tj_csw, c->g.npz));
-    // uniform metrics: nothing to share between levels, one level per wavefront at four wavefronts per SIMD is faster
-    int kpw = c->csw_kpw ? c->csw_kpw : (c->g.geom == 2 ? 1 : 2);
+    const bool uni = c->g.geom == 2;
+    MarchDims md = make_csw_dims(c->g, seg_rows(c, uni ? 24 : 64, c->g.npz));
+    // uniform metrics: nothing to share between levels, one level per wavefront at four wavefronts per SIMD is faster (three and four
+    // levels per wavefront were measured in round 1 and never won)
+    const int kpw = uni ? 1 : 2;
     const int nkg = (c->g.npz + kpw - 1) / kpw;
-    if (c->g.geom == 2 && kpw == 1 && ca.mask_w == 0)   // whole rounds of the chip at four wavefronts per SIMD
+    if (uni && ca.mask_w == 0)   // whole rounds of the chip at four wavefronts per SIMD
       balance_segments(md, nkg, c->g.ny + 4, 4 * c->round_simds, md.tj);
     const int nw = md.nwaves(nkg);
     seg_report("c_sw", md, nkg);
@@ -1689,8 +1566,7 @@ static int csw_march(fv3_ctx *c, const CswArgs &ca) {
     }
     auto go = [&](auto GMc) -> int {
       constexpr int GM = decltype(GMc)::value;
-      if (kpw == 2) return launch_w(c, "c_sw", nw, CswMarch<2, GM>{c->g, ca, md, nkg});
-      return launch_w(c, "c_sw", nw, CswMarch<1, GM>{c->g, ca, md, nkg});
+      return launch_w(c, "c_sw", nw, CswMarch<(GM == 2 ? 1 : 2), GM>{c->g, ca, md, nkg});
     };
     return dispatch_geom(c->g.geom, go);
   }
@@ -1770,7 +1646,7 @@ static bool dsw_momentum_fused(const fv3_ctx *c, const DswArgs &a) {
 static int dsw_transport_march(fv3_ctx *c, const DswArgs &a, int region = 0) {
   const Grid &g = c->g;
   if (ensure_mflux(c)) return 1;
-  MarchDims md = make_march_dims(g, seg_rows(c, c->march_tj, g.npz));
+  MarchDims md = make_march_dims(g, seg_rows(c, kMarchTj, g.npz));
   md.klist = c->klist;
   const int nw = md.nwaves(c->n_plain);
   if (dsw_transport_fused(c, a)) {
@@ -1779,14 +1655,7 @@ static int dsw_transport_march(fv3_ctx *c, const DswArgs &a, int region = 0) {
     MarchDims mf = make_march_dims(g, seg_rows(c, (a.mask_w && !c->tj_env_fused) ? 55 : c->march_tj_fused, g.npz));
     mf.klist = c->klist;
     const int NS = mf.nstrips, NG = mf.nsegs;
-    auto box = [&](int s0, int ns, int g0, int ng) -> int {
-      if (ns <= 0 || ng <= 0) return 0;
-      mf.set_box(s0, ns, g0, ng);
-      // the whole grid in one launch of the branch-free kernel (two wavefronts per SIMD): whole rounds of the chip
-      if (FV3_BF && s0 == 0 && ns == NS && g0 == 0 && ng == NG && a.mask_w == 0)
-        balance_segments(mf, c->n_plain, g.ny, 2 * c->round_simds, mf.tj);
-      const int nwf = mf.nwaves(c->n_plain);
-      seg_report("d_sw_fused", mf, c->n_plain);
+    auto fused_launch = [&](int nwf) -> int {   // mf as it stands: a box or the frame
       return dispatch_hord(a.hord_dp, [&](auto H) {
         constexpr int HORD = decltype(H)::value;
         if (g.geom == 2) {
@@ -1797,19 +1666,19 @@ static int dsw_transport_march(fv3_ctx *c, const DswArgs &a, int region = 0) {
         return launch_w(c, "d_sw_fused", nwf, DswTransportFused<HORD, true, true>{g, a, mf});
       });
     };
+    auto box = [&](int s0, int ns, int g0, int ng) -> int {
+      if (ns <= 0 || ng <= 0) return 0;
+      mf.set_box(s0, ns, g0, ng);
+      // the whole grid in one launch of the branch-free kernel (two wavefronts per SIMD): whole rounds of the chip
+      if (FV3_BF && s0 == 0 && ns == NS && g0 == 0 && ng == NG && a.mask_w == 0)
+        balance_segments(mf, c->n_plain, g.ny, 2 * c->round_simds, mf.tj);
+      seg_report("d_sw_fused", mf, c->n_plain);
+      return fused_launch(mf.nwaves(c->n_plain));
+    };
     if (region == 0 || !dsw_has_interior(c)) return region == 1 ? 0 : box(0, NS, 0, NG);
     if (region == 1) return box(1, NS - 2, 1, NG - 2);
     mf.set_frame();                            // south / north rows and west / east columns in one launch
-    const int nwf = mf.nwaves(c->n_plain);
-    return dispatch_hord(a.hord_dp, [&](auto H) {
-      constexpr int HORD = decltype(H)::value;
-      if (g.geom == 2) {
-        if (a.hydrostatic) return launch_w(c, "d_sw_fused", nwf, DswTransportFused<HORD, false, true, 2>{g, a, mf});
-        return launch_w(c, "d_sw_fused", nwf, DswTransportFused<HORD, true, true, 2>{g, a, mf});
-      }
-      if (a.hydrostatic) return launch_w(c, "d_sw_fused", nwf, DswTransportFused<HORD, false, true>{g, a, mf});
-      return launch_w(c, "d_sw_fused", nwf, DswTransportFused<HORD, true, true>{g, a, mf});
-    });
+    return fused_launch(mf.nwaves(c->n_plain));
   }
   if (region == 1) return 0;  // the per-field kernels are not split
   double *fxs = c->mflux[0], *fys = c->mflux[1];
@@ -1836,7 +1705,7 @@ static int dsw_momentum_march(fv3_ctx *c, const DswArgs &a, int part = 0) {
   const bool fused_m = dsw_momentum_fused(c, a);
   if (!fused_m && !c->ke_scr) RT(work_alloc(c, "ke_scr", 0, &c->ke_scr, g.nB() * g.npz));
   if (fused_m) {
-    MarchDims mf = make_march_dims(g, seg_rows(c, (a.mask_w && !c->tj_env_fused) ? 55 : c->march_tj_mom, g.npz));
+    MarchDims mf = make_march_dims(g, seg_rows(c, (a.mask_w && !c->tj_env_fused) ? 55 : c->march_tj_fused, g.npz));
     mf.klist = c->klist_m;
     if (FV3_BF && a.mask_w == 0)
       balance_segments(mf, c->n_plain_m, g.ny, ((g.geom == 2 && FV3_MOM_3W) ? 3 : 2) * c->round_simds, mf.tj);
@@ -1869,7 +1738,7 @@ static int dsw_momentum_march(fv3_ctx *c, const DswArgs &a, int part = 0) {
     });
   }
   if (part != 2) {
-    MarchDims mk = make_march_dims(g, seg_rows(c, c->march_tj_ke, g.npz));
+    MarchDims mk = make_march_dims(g, seg_rows(c, kMarchTj, g.npz));
     mk.klist = c->klist_m;
     const int nwk = mk.nwaves(c->n_plain_m);
     int rc;
@@ -1884,7 +1753,7 @@ static int dsw_momentum_march(fv3_ctx *c, const DswArgs &a, int part = 0) {
     }
     if (rc || part == 1) return rc;
   }
-  MarchDims md = make_march_dims(g, seg_rows(c, c->march_tj, g.npz));
+  MarchDims md = make_march_dims(g, seg_rows(c, kMarchTj, g.npz));
   md.klist = c->klist_m;
   const int nw = md.nwaves(c->n_plain_m);
   const double *ke = c->ke_scr;
@@ -1903,19 +1772,18 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
   DswCubedState s;
   s.g = g; s.cg = c->cg; s.a = a; s.own_w = 0;
   double **scr[13] = {&s.ut, &s.vt, &s.fx, &s.fy, &s.gxw, &s.gyw, &s.gx, &s.gy, &s.ke, &s.wk, &s.dd, &s.svc, &s.suc};
-  for (int n = 0; n < 13; n++)
-    if (!(*scr[n] = cs_scratch(c, 8 + n))) return fail("d_sw: out of device memory");
+  if (cs_take_n(c, "d_sw", kCsDsw, 13, scr)) return 1;
   const int npz = g.npz, npx = g.npx, npy = g.npy;
   const char *L = "dswc_damp";
   // del-2n damping (cubed_damp.h): the passes of one operator; work arrays = scratch 4..6 of fv_tp_2d (free between its calls)
   auto deln = [&](const double *q, const double *mass, double *fx, double *fy, const int *nord, const double *coef, double thresh,
-                  int corner_area, int nmax, double *out_fx2, double *out_fy2, const PassRegion &rk, int d2_slot = 4) -> int {
+                  int corner_area, int nmax, double *out_fx2, double *out_fy2, const PassRegion &rk, int d2_slot = kCsDelnD2) -> int {
     DelnCubedState d;
     d.g = g; d.q = q; d.mass = mass; d.fx = fx; d.fy = fy; d.nord = nord; d.coef = coef; d.thresh = thresh; d.corner_area = corner_area;
-    d.d2 = cs_scratch(c, d2_slot);
-    d.fx2 = out_fx2 ? out_fx2 : cs_scratch(c, 5);
-    d.fy2 = out_fy2 ? out_fy2 : cs_scratch(c, 6);
-    if (!d.d2 || !d.fx2 || !d.fy2) return fail("d_sw: out of device memory");
+    d.fx2 = out_fx2; d.fy2 = out_fy2;
+    if (cs_take(c, "d_sw", {{d2_slot, &d.d2}}) || (!out_fx2 && cs_take(c, "d_sw", {{kCsDelnFx2, &d.fx2}})) ||
+        (!out_fy2 && cs_take(c, "d_sw", {{kCsDelnFy2, &d.fy2}})))
+      return 1;
     // away from the face corners: the chain in one LDS-tile launch (cubed_damp.h DelnFused); the passes keep the four corner
     // squares of 5 flux points (what the corner maps of copy_corners can reach) and the rim of 3 their intermediates need
     const int wo_d = 5, wm_d = wo_d + 3;
@@ -1946,32 +1814,19 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
     RT(fused_launch());
     return 0;
   };
-  if (!a.hydrostatic && c->lev_has_w_damp_hi) {
-    if (!(s.wfx2 = cs_scratch(c, 25)) || !(s.wfy2 = cs_scratch(c, 26))) return fail("d_sw: out of device memory");
-  }
-  if (c->lev_has_damp_v5) {
-    if (!(s.dfx2 = cs_scratch(c, 22)) || !(s.dfy2 = cs_scratch(c, 23))) return fail("d_sw: out of device memory");
-  }
   const bool heat_pass = c->lev_has_dcon || g.do_diss_est;   // :1462, :1523
-  if (heat_pass) {
-    if (!(s.vortv = cs_scratch(c, 21))) return fail("d_sw: out of device memory");
-  }
-  if (!(a.dddmp < 1.E-5)) {
-    if (!(s.smag = cs_scratch(c, 24))) return fail("d_sw: out of device memory");
-  }
-  if (a.use_cond) {
-    if (!(s.gxq = cs_scratch(c, 27)) || !(s.gyq = cs_scratch(c, 28))) return fail("d_sw: out of device memory");
-  }
+  if (!a.hydrostatic && c->lev_has_w_damp_hi && cs_take(c, "d_sw", {{kCsWfx2, &s.wfx2}, {kCsWfy2, &s.wfy2}})) return 1;
+  if (c->lev_has_damp_v5 && cs_take(c, "d_sw", {{kCsDfx2, &s.dfx2}, {kCsDfy2, &s.dfy2}})) return 1;
+  if (heat_pass && cs_take(c, "d_sw", {{kCsVortv, &s.vortv}})) return 1;
+  if (!(a.dddmp < 1.E-5) && cs_take(c, "d_sw", {{kCsSmag, &s.smag}})) return 1;
+  if (a.use_cond && cs_take(c, "d_sw", {{kCsGxq, &s.gxq}, {kCsGyq, &s.gyq}})) return 1;
   // contravariant winds of the whole face, all levels
-  static const int d1_rows = [] { const char *e = std::getenv("FV3_MI355X_D1_ROWS"); return e ? std::atoi(e) : 1; }();
-  if (d1_rows) {   // the marching form (cubed_dsw.h DswCubedD1aRows); FV3_MI355X_D1_ROWS=0: the point-wise pass
+  {   // the marching form (cubed_dsw.h DswCubedD1aRows; round 6: 0.19 ms against 0.26 point by point)
     Dim3 gr;
     gr.x = (unsigned)((g.ied + 1 - g.isd + 64) / 64);
     gr.y = (unsigned)((g.jed + 1 - g.jsd + 4 * DswCubedD1aRows::kRows) / (4 * DswCubedD1aRows::kRows));
     gr.z = (unsigned)npz;
     RT(launch_p(c, "dswc_d1", gr, 0, DswCubedD1aRows{s}));
-  } else {
-    RT(launch_box(c, "dswc_d1", g.isd, g.ied + 1, g.jsd, g.jed + 1, npz, DswCubedD1a{s}));
   }
   RT(launch_box(c, "dswc_d1b", 0, npx, 0, npy, npz, DswCubedD1b{s}));
   RT(launch_box(c, "dswc_d1c", 0, 3, 0, 0, npz, DswCubedD1c{s}));
@@ -1996,7 +1851,7 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
     if (rg.nk <= 0) return 0;
     // (a marching launch is as long as one wavefront's march whatever its size: below 16 levels -- the two sponge levels of the
     // reference defaults -- the LDS-tile kernel over the face is quicker)
-    const bool march_flux = courant && rg.w == 0 && rg_out.w == 0 && fits && fused_ok && !a.use_cond && frame_fused_on() && flux_march_on() &&
+    const bool march_flux = courant && rg.w == 0 && rg_out.w == 0 && fits && fused_ok && !a.use_cond && flux_march_on() &&
                             g.geom != 2 && rg.nk >= 16;
     if (courant && !march_flux) RT(launch_pass(c, "dswc_d2", g.isd, g.ied, g.jsd, g.jed, PassRegion{0, rg.klist, rg.nk}, DswCubedD2{s}));
     // hybrid frame: delp, w, pt in ONE LDS-tile launch; the whole-face levels too unless a deln_flux damping has to get between
@@ -2011,7 +1866,7 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
       // which overwrites what the march left there; the fields by D4, as after the passes
       const bool dv4 = c->lev_has_damp_v4;
       if (dv4) RT(deln(a.delp, nullptr, nullptr, nullptr, a.lv.nord_v, a.lv.damp_vt, 1.E-4, 0, c->lev_max_nord_v, nullptr, nullptr, rg));
-      const double *dfx = dv4 ? cs_scratch(c, 5) : nullptr, *dfy = dv4 ? cs_scratch(c, 6) : nullptr;
+      const double *dfx = dv4 ? cs_scratch(c, kCsDelnFx2) : nullptr, *dfy = dv4 ? cs_scratch(c, kCsDelnFy2) : nullptr;   // (deln left them there)
       DswArgs am = a;
       am.uc = s.ut; am.vc = s.vt; am.mask_w = wo;
       am.dfx = dfx; am.dfy = dfy; am.dcoef = a.lv.damp_vt;
@@ -2040,7 +1895,7 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
       RT(launch_pass(c, "dswc_d4", g.is, g.ie + 1, g.js, g.je + 1, rg_out, DswCubedD4{so}));
       return 0;
     }
-    if (((rg.w > 0 && rg_out.w > 0) || full_ok) && !a.use_cond && frame_fused_on()) {
+    if (((rg.w > 0 && rg_out.w > 0) || full_ok) && !a.use_cond) {
       TpfField fl[3];
       int nf = 0;
       fl[nf++] = TpfField{a.delp, s.fx, s.fy, a.hord_dp};
@@ -2050,7 +1905,7 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
       if (dv4)   // :919-920 without the final addition: raw fluxes in scratch 5, 6
         RT(deln(a.delp, nullptr, nullptr, nullptr, a.lv.nord_v, a.lv.damp_vt, 1.E-4, 0, c->lev_max_nord_v, nullptr, nullptr, rg));
       RT(tp2d_frame_fused(c, fl, nf, cn_crx, cn_cry, cn_xfx, cn_yfx, rg_out.w + 1, rg.klist, rg.nk, "dswc_tp", rg.w == 0, nullptr, nullptr,
-                          dv4 ? cs_scratch(c, 5) : nullptr, dv4 ? cs_scratch(c, 6) : nullptr, dv4 ? a.lv.damp_vt : nullptr));
+                          dv4 ? cs_scratch(c, kCsDelnFx2) : nullptr, dv4 ? cs_scratch(c, kCsDelnFy2) : nullptr, dv4 ? a.lv.damp_vt : nullptr));
       if (rg.w == 0 && c->lev_has_damp_t)    // :1014-1016: mass-weighted deln_flux inside fv_tp_2d(pt)
         RT(deln(a.pt, a.delp, s.gx, s.gy, a.lv.nord_t, a.lv.damp_t, 1.E-4, 0, c->lev_max_nord_t, nullptr, nullptr, rg));
       if (rg.w == 0 && !a.hydrostatic && c->lev_has_w_damp_hi)   // :950-982: del6_vt_flux(w); nord_w = 0 is formed inside D4
@@ -2125,7 +1980,7 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
       t.g = g; t.cg = c->cg; t.nf = 1; t.override_mask = 0;
       for (int f = 0; f < 4; f++) { t.in[f] = nullptr; t.out[f] = nullptr; t.qx[f] = t.qy[f] = nullptr; t.nlev[f] = 0; t.scale[f] = 1.0; t.top[f] = 0.; }
       t.in[0] = s.wk; t.out[0] = s.smag; t.nlev[0] = npz;
-      if (!(t.qx[0] = cs_scratch(c, 0)) || !(t.qy[0] = cs_scratch(c, 1))) return fail("d_sw: out of device memory");
+      if (cs_take(c, "d_sw", {{kCsA2b, &t.qx[0]}, {kCsA2b + 1, &t.qy[0]}})) return 1;
       if (rg.w == 0 && rg.nk == npz) {   // every level: the hybrid of nh_p_grad's a2b_ord4 (LDS-tile kernel + the passes on a frame)
         A2BCorners<32, 16> kc;
         kc.g = g;
@@ -2141,15 +1996,15 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
     }
     RT(launch_pass(c, L, g.is, g.ie + 1, g.js, g.je + 1, rg, DswCubedD7{so}));
     if (rg.w == 0 && c->lev_has_damp_v5)   // :1513-1515: del6_vt_flux of the RELATIVE vorticity (before D8 adds f0)
-      // (work array 33, not the transports' 4: this chain may run beside theirs, see the lanes below)
-      RT(deln(s.wk, nullptr, nullptr, nullptr, a.lv.nord_v, a.lv.damp_vt, 1.E-5, 1, c->lev_max_nord_v, s.dfx2, s.dfy2, rg, 33));
+      // (a d2 of its own, not the transports': this chain may run beside theirs, see the lanes below)
+      RT(deln(s.wk, nullptr, nullptr, nullptr, a.lv.nord_v, a.lv.damp_vt, 1.E-5, 1, c->lev_max_nord_v, s.dfx2, s.dfy2, rg, kCsVortD2));
     RT(launch_pass(c, "dswc_d8", g.isd, g.ied, g.jsd, g.jed, rg, DswCubedD8{s}));
     }
     if (part == 1) return 0;
-    if (frame_fused_on() && rg.w == 0 && fits && c->use_march && flux_march_on() && rg.nk >= 16) {
+    if (rg.w == 0 && fits && c->use_march && flux_march_on() && rg.nk >= 16) {
       // whole-face levels: the marching fv_tp_2d over the face, then the frame along the edges by the frame kernel (the fluxes are
       // not an input of either: the frame kernel simply overwrites what the march left there)
-      MarchDims md = make_march_dims(g, seg_rows(c, c->march_tj, g.npz));
+      MarchDims md = make_march_dims(g, seg_rows(c, kMarchTj, g.npz));
       md.klist = rg.klist;
       const int nwv = md.nwaves(rg.nk);
       RT(dispatch_hord(a.hord_vt, [&](auto H) {
@@ -2158,11 +2013,9 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
       }));
       const TpfField fl[3] = {TpfField{s.wk, s.gx, s.gy, a.hord_vt}, TpfField{}, TpfField{}};
       RT(tp2d_frame_fused(c, fl, 1, cn_crx, cn_cry, cn_xfx, cn_yfx, wo + 1, rg.klist, rg.nk, "dswc_tpv", false));
-    } else if (frame_fused_on()) {
+    } else {
       const TpfField fl[3] = {TpfField{s.wk, s.gx, s.gy, a.hord_vt}, TpfField{}, TpfField{}};
       RT(tp2d_frame_fused(c, fl, 1, cn_crx, cn_cry, cn_xfx, cn_yfx, rg_out.w + 1, rg.klist, rg.nk, "dswc_tpv", rg.w == 0));
-    } else {
-      RT(tp2d_cubed(c, npz, s.wk, cn_crx, cn_cry, a.hord_vt, s.gx, s.gy, cn_xfx, cn_yfx, nullptr, nullptr, nullptr, nullptr, "dswc_tpv", &rg));
     }
     RT(launch_pass(c, "dswc_d9", g.is, g.ie + 1, g.js, g.je + 1, rg_out, DswCubedD9{so}));
     if (rg.w == 0 && heat_pass) RT(launch_pass(c, "dswc_heat", g.is, g.ie, g.js, g.je, rg_out, DswCubedD10{so}));
@@ -2193,7 +2046,7 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
     // wait for the marching transport kernel's Courant numbers (`mid`) and run beside the momentum kernel.  Measured equal (3.99 -
     // 4.11 against 4.01 - 4.12 ms per C384 L127 pair, profiles/r04_v2_lanes_check.txt), so the variant without the extra pass and
     // the four extra work arrays is the default.
-    static const int lane_d2 = [] { const char *e = std::getenv("FV3_MI355X_LANE_D2"); return e ? std::atoi(e) : 0; }();
+    static const int lane_d2 = env_int("FV3_MI355X_LANE_D2", 0);
     RT(lane_op(c, kLaneFork));
     RT(dsw_transport_march(c, am));                       // main: levels klist[0 : n_plain), Courant numbers too, whole face
     c->lane = 1;
@@ -2203,8 +2056,8 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
     if (!rc && lane_d2) {
       DswCubedState sf = s;
       double *cn[4];
-      for (int n = 0; n < 4; n++)
-        if (!(cn[n] = cs_scratch(c, 29 + n))) rc = fail("d_sw: out of device memory");
+      double **cn_p[4] = {&cn[0], &cn[1], &cn[2], &cn[3]};
+      rc = cs_take_n(c, "d_sw", kCsLaneD2, 4, cn_p);
       if (!rc) {
         sf.a.crx = cn[0]; sf.a.cry = cn[1]; sf.a.xfx = cn[2]; sf.a.yfx = cn[3];
         DswCubedD2 d2{sf};
@@ -2242,7 +2095,7 @@ static int dsw_cubed(fv3_ctx *c, const DswArgs &a) {
   // the divergence, Smagorinsky, the vorticity's del6_vt_flux) reads nothing the transport half writes -- it runs beside it on the side
   // lane; what needs the Courant numbers (the vorticity transport, the wind update, heating) follows on the main lane after the join.
   // The two chains share no work array (the vorticity's damping chain has its own, 33).
-  if (!hyb_t && !hyb_m && !a.use_cond && frame_fused_on() && lanes_pay(c)) {   // (the pass forms of fv_tp_2d share work arrays 4 .. 7)
+  if (!hyb_t && !hyb_m && !a.use_cond && lanes_pay(c)) {   // (the pass forms of fv_tp_2d share work arrays 4 .. 7)
     RT(lane_prepare(c));
     const PassRegion all{0, nullptr, npz};
     RT(lane_op(c, kLaneFork));
@@ -3507,7 +3360,7 @@ extern "C" int fv3_riem_solver_c(fv3_ctx *c, double dt, const fv3_nh_consts *cn,
     if (c->riem_lds) {         // the recurrences in the reference's order: the slab kernel's bits
       RiemFast<true, true> kf{c->g, c->g.npz, dt, to_consts(c, cn), hs, pt, delp, ws, const_cast<double *>(w3), gz,
                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pef, 0, 0, 0};
-      if (const char *pe_ = std::getenv("FV3_MI355X_RIEM_PROBE")) kf.probe = std::atoi(pe_);
+      kf.probe = env_int("FV3_MI355X_RIEM_PROBE", 0);
       RT(launch_p2(c, "riem_solver_c", Dim3{(unsigned)kf.nblocks_x(), (unsigned)kf.nrows(), 1}, kf.kLdsDoubles, kf));
       return 0;
     }
@@ -3563,7 +3416,7 @@ extern "C" int fv3_riem_solver3(fv3_ctx *c, double dt, const fv3_nh_consts *cn, 
     if (c->riem_lds) {
       RiemFast<false, true> kf{c->g, c->g.npz, dt, to_consts(c, cn), zs, pt, delp, ws, w, zh, delz, ppe, pk3, pe, pk, peln, nullptr,
                                use_logp, last_call, fp_out};
-      if (const char *pe_ = std::getenv("FV3_MI355X_RIEM_PROBE")) kf.probe = std::atoi(pe_);
+      kf.probe = env_int("FV3_MI355X_RIEM_PROBE", 0);
       RT(launch_p2(c, "riem_solver3", Dim3{(unsigned)kf.nblocks_x(), (unsigned)kf.nrows(), 1}, kf.kLdsDoubles, kf));
       return 0;
     }
@@ -3606,14 +3459,14 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, int hord, const double *zs, const dou
     RT(launch_c(c, "edge_profile", col_grid((int)(g.nCX() + g.nCY())), kf));
   }
   if (is_cubed(c)) {
-    double *fx = cs_scratch(c, 8), *fy = cs_scratch(c, 9);
-    if (!fx || !fy) return fail("fv3_update_dz_d: out of device memory");
+    double *fx, *fy;
+    if (cs_take(c, "fv3_update_dz_d", {{kCsFx, &fx}, {kCsFy, &fy}})) return 1;
     // Hybrid (see dsw_cubed): the marching transport of the interface heights over the whole face, then the cubed fv_tp_2d
     // passes on the frame along the face edges (zh_out is not an input: the passes simply overwrite the frame)
     const int wo = c->cubed_frame, wm = wo + c->cubed_reach;
     const bool hyb = c->use_march && wo > 0 && g.npx == g.npy && g.npx - 1 >= 2 * wm + 8;
     if (hyb && c->n_plain_z > 0) {
-      MarchDims md = make_march_dims(g, seg_rows(c, c->march_tj, g.npz));
+      MarchDims md = make_march_dims(g, seg_rows(c, kMarchTj, g.npz));
       md.klist = c->klist_z;
       const int nwz = md.nwaves(c->n_plain_z);
       RT(dispatch_hord_all(hord, [&](auto H) {
@@ -3624,28 +3477,19 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, int hord, const double *zs, const dou
     // the plain levels (no damping: klist_z[0 : n_plain_z)): frames when the marching kernel took the interior; the levels
     // with del6_vt_flux damping (nh_utils.F90:268-284): passes on the whole face + the damping fluxes (cubed_damp.h)
     if (c->n_plain_z > 0) {
-      const PassRegion rm{hyb ? wm : 0, c->klist_z, c->n_plain_z}, ro{hyb ? wo : 0, c->klist_z, c->n_plain_z};
-      if (frame_fused_on()) {
-        const TpfField fl[3] = {TpfField{zh_in, fx, fy, hord}, TpfField{}, TpfField{}};
-        RT(tp2d_frame_fused(c, fl, 1, cxa, cya, xfa, yfa, wo + 1, c->klist_z, c->n_plain_z, "zhc_tp", !hyb));
-      } else if (tp2d_cubed(c, km + 1, zh_in, cxa, cya, hord, fx, fy, xfa, yfa, nullptr, nullptr, nullptr, nullptr, "zhc_tp", &rm)) {
-        return 1;
-      }
+      const PassRegion ro{hyb ? wo : 0, c->klist_z, c->n_plain_z};
+      const TpfField fl[3] = {TpfField{zh_in, fx, fy, hord}, TpfField{}, TpfField{}};
+      RT(tp2d_frame_fused(c, fl, 1, cxa, cya, xfa, yfa, wo + 1, c->klist_z, c->n_plain_z, "zhc_tp", !hyb));
       RT(launch_pass(c, "zhc_fin", g.is, g.ie, g.js, g.je, ro, ZhCubedFinal{g, zh_in, fx, fy, xfa, yfa, zh_out}));
     }
     if (c->n_damp_z > 0) {
       const PassRegion rd{0, c->klist_z + c->n_plain_z, c->n_damp_z};
-      if (frame_fused_on()) {
-        const TpfField fl[3] = {TpfField{zh_in, fx, fy, hord}, TpfField{}, TpfField{}};
-        RT(tp2d_frame_fused(c, fl, 1, cxa, cya, xfa, yfa, 5, rd.klist, rd.nk, "zhc_tp", true));
-      } else if (tp2d_cubed(c, km + 1, zh_in, cxa, cya, hord, fx, fy, xfa, yfa, nullptr, nullptr, nullptr, nullptr, "zhc_tp", &rd)) {
-        return 1;
-      }
+      const TpfField fl[3] = {TpfField{zh_in, fx, fy, hord}, TpfField{}, TpfField{}};
+      RT(tp2d_frame_fused(c, fl, 1, cxa, cya, xfa, yfa, 5, rd.klist, rd.nk, "zhc_tp", true));
       DelnCubedState d;
       d.g = g; d.q = zh_in; d.mass = nullptr; d.fx = d.fy = nullptr; d.nord = c->lev_ext_i; d.coef = c->lev_ext_d; d.thresh = 1.E-5;
       d.corner_area = 2;
-      d.d2 = cs_scratch(c, 4); d.fx2 = cs_scratch(c, 10); d.fy2 = cs_scratch(c, 11);
-      if (!d.d2 || !d.fx2 || !d.fy2) return fail("fv3_update_dz_d: out of device memory");
+      if (cs_take(c, "fv3_update_dz_d", {{kCsDelnD2, &d.d2}, {kCsZhFx2, &d.fx2}, {kCsZhFy2, &d.fy2}})) return 1;
       RT(launch_pass(c, "zhc_del6", g.isd, g.ied, g.jsd, g.jed, rd, DelnCubedL1{d}));
       RT(launch_pass(c, "zhc_del6", g.isd, g.ied + 1, g.jsd, g.jed + 1, rd, DelnCubedL24{d, 1, 0}));
       for (int n = 1; n <= c->lev_max_nord_v; n++) {
@@ -3663,7 +3507,7 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, int hord, const double *zs, const dou
   constexpr int TI = FV3_DSW_TI, TJ = FV3_DSW_TJ;
   const bool march = c->use_march != 0;
   if (march && c->n_plain_z > 0) {
-    MarchDims md = make_march_dims(g, seg_rows(c, c->march_tj, g.npz));
+    MarchDims md = make_march_dims(g, seg_rows(c, kMarchTj, g.npz));
     md.klist = c->klist_z;
     const int nwz = md.nwaves(c->n_plain_z);
     RT(dispatch_hord_all(hord, [&](auto H) {
@@ -3922,7 +3766,7 @@ static int run_a2b(fv3_ctx *c, const A2BCorners<TI, TJ> &kf, int nlev_max, const
       s.in[f] = kf.in[f]; s.out[f] = kf.out[f]; s.nlev[f] = kf.nlev[f]; s.scale[f] = kf.scale[f]; s.top[f] = kf.top[f];
       s.qx[f] = s.qy[f] = nullptr;
       if (f < kf.nf) {
-        if (!(s.qx[f] = cs_scratch(c, 2 * f)) || !(s.qy[f] = cs_scratch(c, 2 * f + 1))) return fail("a2b_ord4: out of device memory");
+        if (cs_take(c, "a2b_ord4", {{kCsA2b + 2 * f, &s.qx[f]}, {kCsA2b + 2 * f + 1, &s.qy[f]}})) return 1;
       }
     }
     // Hybrid: away from the face edges a2b_ord4 is the 4th-order form of the LDS-tile kernel (the one-sided forms touch
@@ -4146,7 +3990,7 @@ extern "C" int fv3_geopk(fv3_ctx *c, double ptop, double akap, double cp_air, do
   if (!c || !c->grid_ready) return fail("fv3_geopk: context has no grid");
   const int e = CG ? 1 : 2;
   const int ncol = (c->g.nx + 2 * e) * (c->g.ny + 2 * e);
-  static const int phased_max = [] { const char *v = std::getenv("FV3_MI355X_GEOPK_PHASED"); return v ? std::atoi(v) : 65536; }();
+  static const int phased_max = env_int("FV3_MI355X_GEOPK_PHASED", 65536);
   if (ncol <= phased_max && GeopkPhased::lds_doubles(c->g.npz) * sizeof(double) <= 64 * 1024) {   // small faces: phases over LDS
     GeopkPhased kf{c->g, c->g.npz, CG, ptop, akap, cp_air, ptk, delp, hs, pt, pe, peln, pk, gz, pkz};
     Dim3 gr;
@@ -4274,14 +4118,7 @@ extern "C" int fv3_set_remap_te(fv3_ctx *c, int remap_te, const double *hs, doub
   return 0;
 }
 
-static int remap_two_waves() {   // FV3_MI355X_REMAP_2W=0: the scalars' remap kernel without the two-wavefronts-per-SIMD register budget
-  static const int v = [] { const char *e = std::getenv("FV3_MI355X_REMAP_2W"); return e ? std::atoi(e) : 1; }();
-  return v;
-}
-static int remap_probe() {
-  const char *e = std::getenv("FV3_MI355X_REMAP_PROBE");
-  return e ? std::atoi(e) : 0;
-}
+static int remap_probe() { return env_int("FV3_MI355X_REMAP_PROBE", 0); }
 extern "C" int fv3_lagrangian_to_eulerian(fv3_ctx *c, const fv3_remap_params *p, const int *kord_tr, double *ps,
                                           double *pe, double *delp, double *pkz, double *pk, double *u, double *v,
                                           double *w, double *delz, double *pt, double *q, double *peln, double *omga,
@@ -4348,13 +4185,13 @@ extern "C" int fv3_lagrangian_to_eulerian(fv3_ctx *c, const fv3_remap_params *p,
         const Dim3 gr{(unsigned)((g.nx + kFC - 1) / kFC), (unsigned)g.ny, 1};
         if (p->hydrostatic) {
           using K = RemapFastScalars<true, false, L>;
-          RT((remap_two_waves() || L == 5 ? launch_p2<K> : launch_p<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga, remap_probe()}));
+          RT((launch_p2<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga, remap_probe()}));
         } else if (moist) {   // use_cond / moist_kappa (fv3_set_moist): cappa from moist_cv in the temperature transform and in pkz
           using K = RemapFastScalars<false, true, L>;
           RT((launch_p2<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga, remap_probe()}));
         } else {
           using K = RemapFastScalars<false, false, L>;
-          RT((remap_two_waves() || L == 5 ? launch_p2<K> : launch_p<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga, remap_probe()}));
+          RT((launch_p2<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga, remap_probe()}));
         }
       }
       {
@@ -4395,8 +4232,9 @@ extern "C" int fv3_lagrangian_to_eulerian(fv3_ctx *c, const fv3_remap_params *p,
   if (c->remap_te_on) {   // fv_mapz.F90:232-286: the energy of every layer from the un-remapped state; u kept for the rows above
     if (!p->hydrostatic && (!w || !delz)) return fail("fv3_lagrangian_to_eulerian: remap_te (nonhydrostatic) needs w and delz");
     if (p->sphum > 0 && !q) return fail("fv3_lagrangian_to_eulerian: remap_te with sphum > 0 needs the tracers");
-    double *u_old = cs_scratch(c, 30);
-    if (!u_old || need_scratch(c, 1)) return fail("fv3_lagrangian_to_eulerian: out of device memory");
+    double *u_old;
+    if (cs_take(c, "fv3_lagrangian_to_eulerian", {{kCsRemapUOld, &u_old}})) return 1;
+    if (need_scratch(c, 1)) return fail("fv3_lagrangian_to_eulerian: out of device memory");
     rp.remap_te = 1; rp.hs = c->rte_hs; rp.te = c->rte_te; rp.u_old = u_old;
     RT(fv3_memcpy_d2d(c, u_old, u, sizeof(double) * g.nU() * (size_t)km));
     RemapTePre kf{g, km, rp, u, v, w, delz, pt, delp, q, pe, pk, peln, pkz, c->scratch[0]};
@@ -4535,8 +4373,8 @@ extern "C" int fv3_d_sw_inline_q(fv3_ctx *c, int nq, int hord_tr, int nord_t, do
   }
   const double *mass = nullptr;
   if (damp_t > 1.e-4) {
-    double *m = cs_scratch(c, 29);
-    if (!m) return fail("fv3_d_sw_inline_q: out of device memory");
+    double *m;
+    if (cs_take(c, "fv3_d_sw_inline_q", {{kCsInlineQMass, &m}})) return 1;
     InlineQMass kf{g, delp_old, delp_new, m};
     Dim3 grid;
     grid.x = (unsigned)((g.nA() + InlineQMass::CH - 1) / InlineQMass::CH);
@@ -4746,7 +4584,7 @@ static int tracer_step_impl(fv3_ctx *c, int it, int nsplt, const int *ksplt_dev,
         return go(H, std::integral_constant<int, 2>{});
       });
     }
-    MarchDims md = make_march_dims(g, seg_rows(c, c->march_tj, g.npz));
+    MarchDims md = make_march_dims(g, seg_rows(c, kMarchTj, g.npz));
     const int nwt = md.nwaves(g.npz * nq);
     return dispatch_hord_all(hord, [&](auto H) {
       TracerMarch<decltype(H)::value> kf{g, md, g.npz, nq, it, nsplt, ksplt_dev, q, dp1, mfx, mfy, cx, cy, xfx, yfx,
@@ -4755,8 +4593,8 @@ static int tracer_step_impl(fv3_ctx *c, int it, int nsplt, const int *ksplt_dev,
     });
   };
   if (is_cubed(c)) {
-    double *fx = cs_scratch(c, 8), *fy = cs_scratch(c, 9);
-    if (!fx || !fy) return fail("fv3_tracer_2d_step: out of device memory");
+    double *fx, *fy;
+    if (cs_take(c, "fv3_tracer_2d_step", {{kCsFx, &fx}, {kCsFy, &fy}})) return 1;
     const bool damp = it == 1 && trdm > 1.e-4;      // fv_tracer2d.F90:497-505: deln_flux inside fv_tp_2d, mass = dp1
     int *nord_dev = nullptr;
     double *coef_dev = nullptr;
@@ -4777,18 +4615,13 @@ static int tracer_step_impl(fv3_ctx *c, int it, int nsplt, const int *ksplt_dev,
     const PassRegion rm{hyb ? wm : 0, nullptr, g.npz}, ro{hyb ? wo : 0, nullptr, g.npz};
     const size_t nq3 = (size_t)g.npz * g.nA();
     for (int iq = 0; iq < nq; iq++) {
-      if (frame_fused_on()) {
-        const TpfField fl[3] = {TpfField{q + iq * nq3, fx, fy, hord}, TpfField{}, TpfField{}};
-        RT(tp2d_frame_fused(c, fl, 1, cx, cy, xfx, yfx, wo + 1, nullptr, g.npz, "trc_tp", !hyb, mfx, mfy));
-      } else if (tp2d_cubed(c, g.npz, q + iq * nq3, cx, cy, hord, fx, fy, xfx, yfx, nullptr, nullptr, mfx, mfy, "trc_tp", &rm)) {
-        return 1;
-      }
+      const TpfField fl[3] = {TpfField{q + iq * nq3, fx, fy, hord}, TpfField{}, TpfField{}};
+      RT(tp2d_frame_fused(c, fl, 1, cx, cy, xfx, yfx, wo + 1, nullptr, g.npz, "trc_tp", !hyb, mfx, mfy));
       if (damp) {
         DelnCubedState d;
         d.g = g; d.q = q + iq * nq3; d.mass = mass ? mass : dp1; d.fx = fx; d.fy = fy; d.nord = nord_dev; d.coef = coef_dev; d.thresh = 1.E-4;
         d.corner_area = 0;
-        d.d2 = cs_scratch(c, 4); d.fx2 = cs_scratch(c, 5); d.fy2 = cs_scratch(c, 6);
-        if (!d.d2 || !d.fx2 || !d.fy2) return fail("fv3_tracer_2d_step: out of device memory");
+        if (cs_take(c, "fv3_tracer_2d_step", {{kCsDelnD2, &d.d2}, {kCsDelnFx2, &d.fx2}, {kCsDelnFy2, &d.fy2}})) return 1;
         RT(launch_pass(c, "trc_deln", g.isd, g.ied, g.jsd, g.jed, rm, DelnCubedL1{d}));
         RT(launch_pass(c, "trc_deln", g.isd, g.ied + 1, g.jsd, g.jed + 1, rm, DelnCubedL24{d, 1, 0}));
         for (int n = 1; n <= nord_tr; n++) {

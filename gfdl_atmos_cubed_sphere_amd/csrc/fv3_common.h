@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 
 #ifdef FV3_HOST_EMU
 #define FV3_HD inline
@@ -61,6 +62,14 @@ FV3_HD double dexp(double x) { return fv3_exp(x); }
 FV3_HD double dlog(double x) { return fv3_log(x); }
 
 constexpr int NG = 3;  // halo width (tools/fv_mp_mod.F90:61)
+
+// an integer environment switch (docs/SWITCHES.md): its value, or `def` where it is unset.  Every switch of the library is read
+// through here; whether once per process (a function-local static) or once per context (ctx_switches, fv3_api.hip) is the caller's.
+inline int env_int(const char *name, int def, bool *is_set = nullptr) {
+  const char *e = std::getenv(name);
+  if (is_set) *is_set = e != nullptr;
+  return e ? std::atoi(e) : def;
+}
 
 // Device-side view of the domain + gridstruct (all pointers are device pointers).
 struct Grid {

@@ -163,37 +163,22 @@ inline int launch_2w(Dim3 grid, size_t lds_doubles, stream_t s, const F &f) {
 // CUs 2 or 3 groups each).  The functor still sees the (group of 256, thread) numbering of the tile launcher.
 // Their k loops are chains of dependent, data-dependent loads, so what bounds them is the number of wavefronts a SIMD can
 // switch between, not lanes: with `lanes` < 64 only the first `lanes` threads of each 64-thread group take a column, which
-// multiplies the wavefronts in flight by 64 / lanes (FV3_MI355X_COL_LANES, measured best value is the default).
+// multiplies the wavefronts in flight by 64 / lanes (measured best: all 64, the default of a launch that does not ask).
 // Workgroups go to the 8 XCDs in turn (linear workgroup index mod 8).  A column kernel reads its neighbours' columns (rows j - 1, j + 1
 // are six or seven 64-column workgroups away): with chunk > 0 (= workgroups per XCD) workgroup b of the first 8 chunk takes the logical
 // index (XCD of b) * chunk + b / 8, so an XCD works through one contiguous range of columns and the neighbour rows meet in its own L2
-// (FV3_MI355X_COL_XCD=0: the plain order).  `face`: the group kernels' blockIdx.y, whose workgroups continue the round-robin.
+// (round 6: p_grad_c -16 % against the plain order).  `face`: the group kernels' blockIdx.y, whose workgroups continue the round-robin.
 __device__ __forceinline__ int col_block(int chunk, int face = 0) {
   const int b = (int)blockIdx.x;
   if (b >= chunk * 8) return b;
   const int xcd = (b + face * (int)gridDim.x) & 7;
   return xcd * chunk + (b >> 3);
 }
-inline int col_xcd() {
-  static const int v = [] {
-    const char *e = std::getenv("FV3_MI355X_COL_XCD");
-    return e ? std::atoi(e) : 1;
-  }();
-  return v;
-}
 template <class F>
 __global__ void __launch_bounds__(64) col_kernel(const F f, int lanes, int chunk) {
   if ((int)threadIdx.x >= lanes) return;
   const int vt = col_block(chunk) * lanes + (int)threadIdx.x;  // virtual thread = column slot
   f(vt >> 8, 0, 0, vt & 255, nullptr);
-}
-inline int col_lanes() {
-  static const int v = [] {
-    const char *e = std::getenv("FV3_MI355X_COL_LANES");
-    const int n = e ? std::atoi(e) : 64;
-    return (n == 16 || n == 32) ? n : 64;
-  }();
-  return v;
 }
 // the same under a register budget of W wavefronts per SIMD (512 / W VGPRs): the column kernels wait on memory in a loop
 // that is sequential in k, so for some of them more wavefronts in flight are worth a few spilled registers
@@ -203,12 +188,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W, W)))
   const int vt = col_block(chunk) * lanes + (int)threadIdx.x;
   f(vt >> 8, 0, 0, vt & 255, nullptr);
 }
-// lanes_req > 0: columns per wavefront of this launch (any value <= 64; the default is col_lanes())
+// lanes_req > 0: columns per wavefront of this launch (any value <= 64; the default is 64)
 template <int W = 0, class F>
 inline int launch_cols(Dim3 grid, stream_t s, const F &f, int lanes_req = 0) {
-  const int lanes = (lanes_req > 0 && lanes_req <= 64) ? lanes_req : col_lanes();
+  const int lanes = (lanes_req > 0 && lanes_req <= 64) ? lanes_req : 64;
   const unsigned nb = (unsigned)(((size_t)grid.x * 256 + lanes - 1) / lanes);
-  const int chunk = (col_xcd() && nb >= 64) ? (int)(nb >> 3) : 0;
+  const int chunk = nb >= 64 ? (int)(nb >> 3) : 0;
   if constexpr (W > 0)
     hipLaunchKernelGGL((col_kernel_w<F, W>), dim3(nb), dim3(64), 0, s, f, lanes, chunk);
   else
@@ -225,13 +210,6 @@ __device__ __forceinline__ int wave_index(int chunk) {
   const int b = (int)blockIdx.x;
   const int lb = chunk > 0 ? (b % kXcds) * chunk + b / kXcds : b;
   return lb * (kNT / 64) + (int)(threadIdx.x >> 6);
-}
-inline int xcd_remap() {
-  static const int v = [] {
-    const char *e = std::getenv("FV3_MI355X_XCD_REMAP");
-    return e ? std::atoi(e) : 1;
-  }();
-  return v;
 }
 template <class F>
 __global__ void __launch_bounds__(kNT) wave_kernel(const F f, int nwaves, int chunk) {
@@ -266,7 +244,7 @@ template <class F>
 inline int launch_waves(int nwaves, stream_t s, const F &f) {
   const int wpb = kNT / 64;
   int nblocks = (nwaves + wpb - 1) / wpb, chunk = 0;
-  if (xcd_remap() && nblocks >= 4 * kXcds) {
+  if (nblocks >= 4 * kXcds) {
     chunk = (nblocks + kXcds - 1) / kXcds;
     nblocks = chunk * kXcds;
   }
@@ -361,7 +339,7 @@ inline int launch_group(Dim3 grid, size_t lds_doubles, int a, stream_t s, const 
   } else {
     const int wpb = kNT / 64;
     int nblocks = (a + wpb - 1) / wpb, chunk = 0;
-    if (xcd_remap() && nblocks >= 4 * kXcds) {
+    if (nblocks >= 4 * kXcds) {
       chunk = (nblocks + kXcds - 1) / kXcds;
       nblocks = chunk * kXcds;
     }
@@ -379,9 +357,9 @@ template <int W, class F>
 inline int launch_group_cols(Dim3 grid, int lanes_req, stream_t s, const F *const *fs, int n) {
   FGroup<F> fg;
   fgroup_fill(fg, fs, n);
-  const int lanes = (lanes_req > 0 && lanes_req <= 64) ? lanes_req : col_lanes();
+  const int lanes = (lanes_req > 0 && lanes_req <= 64) ? lanes_req : 64;
   const unsigned nb = (unsigned)(((size_t)grid.x * 256 + lanes - 1) / lanes);
-  const int chunk = (col_xcd() && nb >= 64) ? (int)(nb >> 3) : 0;
+  const int chunk = nb >= 64 ? (int)(nb >> 3) : 0;
   if constexpr (W > 0)
     hipLaunchKernelGGL((col_kernel_w_g<F, W>), dim3(nb, (unsigned)n), dim3(64), 0, s, fg, lanes, chunk);
   else

@@ -132,10 +132,7 @@ struct MarchDims {
   }
 };
 inline int march_k_fast() {
-  static const int v = [] {
-    const char *e = std::getenv("FV3_MI355X_K_FAST");
-    return e ? std::atoi(e) : 0;  // measured: no gain on MI355X (metric rows are served by L2 / Infinity Cache either way)
-  }();
+  static const int v = env_int("FV3_MI355X_K_FAST", 0);  // measured: no gain on MI355X (metric rows are served by L2 / Infinity Cache either way)
   return v;
 }
 inline MarchDims make_march_dims(const Grid &g, int tj) {
