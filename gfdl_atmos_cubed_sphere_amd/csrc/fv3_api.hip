@@ -29,6 +29,7 @@
 #include "nh_alt.h"
 #include "neg_adj.h"
 #include "subgrid_z.h"
+#include "diag_kernels.h"
 #include "remap_kernels.h"
 #include "remap_fast.h"
 #include "tracer_kernels.h"
@@ -4558,6 +4559,20 @@ extern "C" int fv3_update_dwinds_phys(fv3_ctx *c, double dt, const double *u_dt,
   grid.z = (unsigned)g.npz;
   if (sphere) RT(launch_p(c, "update_dwinds_phys", grid, 0, UpdateDwindsPhys<true>{g, c->dw, 0.5 * dt, u_dt, v_dt, u, v}));
   else RT(launch_p(c, "update_dwinds_phys", grid, 0, UpdateDwindsPhys<false>{g, DwindsGeom{}, 0.5 * dt, u_dt, v_dt, u, v}));
+  return 0;
+}
+
+// ---- fv_diag: a field at one pressure level (diag_kernels.h) ----------------------------------------------------------------------
+extern "C" int fv3_interpolate_vertical(fv3_ctx *c, int km, double plev, const double *peln, const double *a3, int in_ng, double *a2) {
+  FV3_ENTRY(c);
+  if (!c || !c->grid_ready) return fail("fv3_interpolate_vertical: context has no grid");
+  if (!peln || !a3 || !a2) return fail("fv3_interpolate_vertical: null argument");
+  if (km < 1) return fail("fv3_interpolate_vertical: km = %d < 1", km);
+  if (!(plev > 0.)) return fail("fv3_interpolate_vertical: plev must be positive");
+  const Grid &g = c->g;
+  if (in_ng != 0 && in_ng != g.is - g.isd)
+    return fail("fv3_interpolate_vertical: in_ng = %d is neither 0 (compute domain) nor the halo width %d", in_ng, g.is - g.isd);
+  RT(launch_c(c, "interpolate_vertical", col_grid(g.nx * g.ny), InterpolateVertical{g, km, in_ng, std::log(plev), peln, a3, a2}));
   return 0;
 }
 

@@ -26,6 +26,7 @@ module fv3_mi355x_mod
   public :: fv3_c2l, fv3_rayleigh_u2f, fv3_rayleigh_apply, fv3_rayleigh_super, fv3_compute_total_energy, fv3_energy_fixer_sums, fv3_remap_finish, fv3_ordered_sum, fv3_adv_pe, fv3_set_condensate, fv3_registry_mode, fv3_registry_put, fv3_registry_get, fv3_registry_host_touched, fv3_registry_fetch, fv3_registry_forget, fv3_registry_stats, fv3_set_fast_tau_w, fv3_set_ray_fast, fv3_ray_fast, fv3_mix_dp, fv3_compute_aam, fv3_consv_am_apply, fv3_set_moist, fv3_moist_params
   public :: fv3_neg_adj3, fv3_neg_adj_params
   public :: fv3_fv_subgrid_z, fv3_sg_params, fv3_grid_dwinds, fv3_grid_upload_dwinds, fv3_update_dwinds_phys
+  public :: fv3_interpolate_vertical
 
   type, bind(C) :: fv3_domain
     integer(c_int) :: is, ie, js, je, ng, npx, npy, npz, grid_type
@@ -676,6 +677,15 @@ module fv3_mi355x_mod
       import :: c_int, c_ptr, c_double
       type(c_ptr), value :: ctx, u_dt, v_dt, u, v
       real(c_double), value :: dt
+    end function
+    ! interpolate_vertical (tools/fv_diagnostics.F90:4910-4948): a3 (km layers) at the pressure plev [Pa] into a2 (is:ie, js:je).
+    ! in_ng = 0: a3 on the compute domain, as the reference's argument; in_ng = ng: a state field with its halo, in the place of the
+    ! section Atm%pt(isc:iec, jsc:jec, :) the reference's callers pass
+    integer(c_int) function fv3_interpolate_vertical(ctx, km, plev, peln, a3, in_ng, a2) bind(C, name="fv3_interpolate_vertical")
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: ctx, peln, a3, a2
+      integer(c_int), value :: km, in_ng
+      real(c_double), value :: plev
     end function
     integer(c_int) function fv3_set_ak_bk(ctx, ak, bk) bind(C, name="fv3_set_ak_bk")
       import :: c_int, c_ptr, c_double

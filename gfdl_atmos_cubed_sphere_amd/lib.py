@@ -37,7 +37,7 @@ EXPORTS = ["fv3_last_error", "fv3_create", "fv3_destroy", "fv3_set_stream", "fv3
            "fv3_set_dp_ref", "fv3_update_dz_c", "fv3_set_condensate", "fv3_set_fast_tau_w", "fv3_set_ray_fast", "fv3_ray_fast", "fv3_mix_dp", "fv3_compute_aam", "fv3_consv_am_apply", "fv3_riem_solver_c", "fv3_update_dz_d", "fv3_riem_solver3",
            "fv3_p_grad_c", "fv3_nh_p_grad", "fv3_split_p_grad", "fv3_grad1_p_update", "fv3_d_sw_inline_q", "fv3_flux_accum", "fv3_fill2d_mass", "fv3_fill2d_apply", "fv3_set_remap_te", "fv3_profile_report_timers", "fv3_prt_maxmin", "fv3_pk3_halo", "fv3_pe_halo", "fv3_geopk", "fv3_zh_from_delz", "fv3_set_ak_bk", "fv3_set_moist", "fv3_lagrangian_to_eulerian",
            "fv3_tracer_2d_prep", "fv3_tracer_2d_scale", "fv3_tracer_2d_step", "fv3_neg_adj3",
-           "fv3_fv_subgrid_z", "fv3_grid_upload_dwinds", "fv3_update_dwinds_phys"]
+           "fv3_fv_subgrid_z", "fv3_grid_upload_dwinds", "fv3_update_dwinds_phys", "fv3_interpolate_vertical"]
 
 
 class Fv3Error(RuntimeError):
@@ -478,6 +478,12 @@ class Context:
             self.upload_dwinds()
         self.lib.check(self.lib.dll.fv3_update_dwinds_phys(self.h, C.c_double(dt), _pp(u_dt), _pp(v_dt), _pp(u), _pp(v)),
                        "fv3_update_dwinds_phys")
+
+    def interpolate_vertical(self, km, plev, peln, a3, a2, in_ng=0):
+        """interpolate_vertical (tools/fv_diagnostics.F90:4910-4948): a2 (is:ie, js:je) = a3 (km layers) at the pressure plev [Pa], linear
+        in the layer-mean log pressure of peln (is:ie, km+1, js:je).  in_ng: 0 = a3 on the compute domain, ng = a state field with halo"""
+        self.lib.check(self.lib.dll.fv3_interpolate_vertical(self.h, C.c_int(km), C.c_double(plev), _pp(peln), _pp(a3), C.c_int(in_ng),
+                                                             _pp(a2)), "fv3_interpolate_vertical")
 
     def profile(self, enable: bool):
         self.lib.check(self.lib.dll.fv3_profile(self.h, C.c_int(int(enable))), "fv3_profile")

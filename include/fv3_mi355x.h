@@ -703,6 +703,18 @@ int fv3_grid_upload_dwinds(fv3_ctx *ctx, const fv3_grid_dwinds *g);
  * (bounded_domain: the edge blend is switched off there). */
 int fv3_update_dwinds_phys(fv3_ctx *ctx, double dt, const double *u_dt, const double *v_dt, double *u, double *v);
 
+/* fv3_interpolate_vertical -- interpolate_vertical, tools/fv_diagnostics.F90:4910-4948 (call sites :2017 the 850 hPa vorticity, :2198 and :2263-2299
+ * the relative humidity at 200 hPa and at ten CMIP levels, :2971-2979 condensate at 200 / 500 / 850 hPa, :3522): the field a3 (km layers) at the one pressure plev [Pa], linear in the layer-mean log pressure
+ * pm(k) = 0.5 (peln(k) + peln(k+1)) (:4930); at or above pm(1) it is a3(1), at or below pm(km) it is a3(km) (:4933-4936).
+ * log(plev) is taken once on the host, as the reference does (:4922).  is, ie, js, je are the context's.
+ * peln: (is:ie, km+1, js:je).  a2: (is:ie, js:je), written whole; nothing else is written.  Device pointers.
+ * in_ng: the layout of a3.  0 = an array on the compute domain, (is:ie, js:je, km), as the reference's argument; ng = a state field
+ * in the A layout with its halo -- the reference's callers pass the section Atm%pt(isc:iec, jsc:jec, :), which on the device would
+ * be a copy.  Any other value is refused.
+ * One launch (six faces of an fv3_group: one); no work array.
+ * Refused (status 1 and a message, nothing launched): null pointers, km < 1, plev <= 0, in_ng other than 0 or ng. */
+int fv3_interpolate_vertical(fv3_ctx *ctx, int km, double plev, const double *peln, const double *a3, int in_ng, double *a2);
+
 /* Per-kernel timing with HIP events recorded on the context's stream around every kernel the
  * library launches (this is what bench.py's roofline figures are measured with).  report: one line
  * "label count total_ms" per kernel label since the last report; synchronises the stream. */
