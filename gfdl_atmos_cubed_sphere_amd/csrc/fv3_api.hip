@@ -29,6 +29,7 @@
 #include "nh_alt.h"
 #include "neg_adj.h"
 #include "subgrid_z.h"
+#include "phys_update.h"
 #include "diag_kernels.h"
 #include "remap_kernels.h"
 #include "remap_fast.h"
@@ -159,6 +160,9 @@ struct fv3_ctx {
   DwindsGeom dw{};
   double *dw_dev = nullptr;
   bool dw_ready = false;
+  // fv_update_phys (phys_update.h): qstar(k), p_fac(k) of the tau_h2o relaxation, 2 x npz on the device, and what was uploaded last
+  double *up_tab = nullptr;
+  std::vector<double> up_tab_host;
   std::vector<double> host_area;   // prt_maxmin: area on the host, and g_sum's global_area
   double global_area = 0.;
   int march_tj_fused = kMarchTj;   // rows per segment of the fused d_sw kernels, transports and momentum (FV3_MI355X_MARCH_TJ_FUSED)
@@ -702,6 +706,7 @@ extern "C" int fv3_destroy(fv3_ctx *c) {
   if (c->cg_dev) rt_free(c->cg_dev);
   work_free(c, &c->sg_wk);
   if (c->dw_dev) rt_free(c->dw_dev);
+  if (c->up_tab) rt_free(c->up_tab);
   if (c->stream2) rt_stream_destroy(c->stream2);
   if (c->ev_fork) rt_event_destroy(c->ev_fork);
   if (c->ev_join) rt_event_destroy(c->ev_join);
@@ -4559,6 +4564,131 @@ extern "C" int fv3_update_dwinds_phys(fv3_ctx *c, double dt, const double *u_dt,
   grid.z = (unsigned)g.npz;
   if (sphere) RT(launch_p(c, "update_dwinds_phys", grid, 0, UpdateDwindsPhys<true>{g, c->dw, 0.5 * dt, u_dt, v_dt, u, v}));
   else RT(launch_p(c, "update_dwinds_phys", grid, 0, UpdateDwindsPhys<false>{g, DwindsGeom{}, 0.5 * dt, u_dt, v_dt, u, v}));
+  return 0;
+}
+
+// ---- fv_update_phys: the column part (phys_update.h) ------------------------------------------------------------------------------
+extern "C" int fv3_fv_update_phys(fv3_ctx *c, const fv3_update_phys_params *p, const double *u_dt, const double *v_dt, const double *t_dt, double *q_dt,
+                                  double *delp, double *pt, double *q, double *qdiag, double *ua, double *va, const double *w, double *delz,
+                                  double *ps, double *pe, double *peln, double *pk, double *pkz, double *u_srf, double *v_srf) {
+  FV3_ENTRY(c);
+  if (!c || !c->grid_ready) return fail("fv3_fv_update_phys: context has no grid");
+  if (!p || !u_dt || !v_dt || !t_dt || !delp || !pt || !ua || !va || !ps || !pe || !peln || !pk || !u_srf || !v_srf)
+    return fail("fv3_fv_update_phys: null parameters / field");
+  const Grid &g = c->g;
+  if (g.npz < 1) return fail("fv3_fv_update_phys: npz = %d < 1", g.npz);
+  const int nw = p->nwat;
+  if (nw < 0) return fail("fv3_fv_update_phys: nwat = %d < 0", nw);
+  if (p->nq < 0 || p->ncnst < p->nq) return fail("fv3_fv_update_phys: nq = %d, ncnst = %d: 0 <= nq <= ncnst is needed", p->nq, p->ncnst);
+  if (p->ncnst > 64) return fail("fv3_fv_update_phys: ncnst = %d > 64 tracers is not built", p->ncnst);
+  if (p->hydrostatic && !pkz) return fail("fv3_fv_update_phys: hydrostatic needs pkz");
+  if (!p->hydrostatic && (!w || !delz)) return fail("fv3_fv_update_phys: nonhydrostatic needs w and delz");
+  const bool has_qdt = q_dt != nullptr;
+  if (has_qdt) {
+    if (nw > p->nq) return fail("fv3_fv_update_phys: nwat = %d > nq = %d: the sum of the water tendencies (:337) would leave q_dt", nw, p->nq);
+    if (p->nq > 0 && !q) return fail("fv3_fv_update_phys: null q with q_dt");
+    if (p->ncnst > p->nq && nw != 0 && !qdiag) return fail("fv3_fv_update_phys: null qdiag with ncnst = %d > nq = %d", p->ncnst, p->nq);
+    if (p->ncnst > 0 && nw != 0 && !p->adjust_mass) return fail("fv3_fv_update_phys: null adjust_mass");
+  }
+  if (!(p->dt == p->dt)) return fail("fv3_fv_update_phys: dt is not a number");
+  // :375-428: the temperature branch, and the branch set of moist_cp / moist_cv it calls (none in the gama_dt branch)
+  const int tb = p->hydrostatic ? 0 : (p->phys_hydrostatic ? 1 : (nw == 0 ? 2 : 3));
+  const int nwc = (tb == 2 || nw < 2 || nw > 6) ? 0 : nw;
+  const bool relax = has_qdt && p->tau_h2o != 0.;
+  const struct { const char *name; int idx; bool need; } sp[6] = {
+      {"sphum", p->sphum, nwc != 0 || relax},
+      {"liq_wat", p->liq_wat, nwc != 0},
+      {"rainwat", p->rainwat, nwc >= 4},
+      {"ice_wat", p->ice_wat, nwc == 3 || nwc >= 5},
+      {"snowwat", p->snowwat, nwc >= 5},
+      {"graupel", p->graupel, nwc == 6}};
+  for (const auto &s : sp)
+    if (s.need && (s.idx < 1 || s.idx > p->ncnst || s.idx > p->nq))
+      return fail("fv3_fv_update_phys: nwat = %d%s needs %s, whose index %d is outside 1..ncnst = %d (and the nq = %d tracers of q)", nw,
+                  relax ? " with tau_h2o" : "", s.name, s.idx, p->ncnst, p->nq);
+  if (nwc != 0 && !q) return fail("fv3_fv_update_phys: null q: the heat capacities of nwat = %d read it", nw);
+  if (p->cld_amt < 0 || p->cld_amt > p->ncnst || p->w_diff < 0 || p->w_diff > p->ncnst)
+    return fail("fv3_fv_update_phys: cld_amt = %d / w_diff = %d outside 0..ncnst = %d", p->cld_amt, p->w_diff, p->ncnst);
+  const int w_diff = p->hydrostatic ? 0 : p->w_diff;   // :197-202
+  unsigned long long adj = 0;   // :357
+  if (has_qdt && nw != 0)
+    for (int m = 1; m <= p->ncnst; m++)
+      if (m != p->cld_amt && m != w_diff && p->adjust_mass[m - 1]) adj |= 1ull << (m - 1);
+  const double *qstar_dev = nullptr, *pfac_dev = nullptr;
+  if (relax) {   // :222, :280-310: qstar(k), p_fac(k) from pfull(k) of get_eta_level(npz, 1.E5, ...) (tools/fv_eta.F90:1923-1954)
+    if (!p->ak || !p->bk) return fail("fv3_fv_update_phys: tau_h2o = %g needs ak and bk", p->tau_h2o);
+    const int npz = g.npz;
+    const double q1_h2o = 2.2E-6, q7_h2o = 3.8E-6, q100_h2o = 3.8E-6, q1000_h2o = 3.1E-6, q2000_h2o = 2.8E-6, q3000_h2o = 3.0E-6;
+    std::vector<double> tab(2 * (size_t)npz, 0.), ph(npz + 1);
+    ph[0] = p->ak[0];
+    for (int k = 1; k <= npz; k++) ph[k] = p->ak[k] + p->bk[k] * 1.0E5;
+    for (int k = 0; k < npz; k++) {
+      const double pf = (k == 0 && !(p->ak[0] > 1.E-8)) ? (ph[1] - ph[0]) * p->kappa / (p->kappa + 1.) : (ph[k + 1] - ph[k]) / std::log(ph[k + 1] / ph[k]);
+      double qstar = 0., fac = 0.;
+      const double tau = p->tau_h2o;
+      if (tau < 0.0 && pf < 100.E2) {
+        qstar = 3.E-6;
+        fac = -tau * 86400.;
+      } else if (tau > 0.0 && pf < 3000.) {
+        if (pf < 1.) {
+          qstar = q1_h2o;
+          fac = 0.2 * tau * 86400.;
+        } else if (pf < 7. && pf >= 1.) {
+          qstar = q1_h2o + (q7_h2o - q1_h2o) * std::log(pf / 1.) / std::log(7.);
+          fac = 0.3 * tau * 86400.;
+        } else if (pf < 100. && pf >= 7.) {
+          qstar = q7_h2o + (q100_h2o - q7_h2o) * std::log(pf / 7.) / std::log(100. / 7.);
+          fac = 0.4 * tau * 86400.;
+        } else if (pf < 1000. && pf >= 100.) {
+          qstar = q100_h2o + (q1000_h2o - q100_h2o) * std::log(pf / 1.E2) / std::log(10.);
+          fac = 0.5 * tau * 86400.;
+        } else if (pf < 2000. && pf >= 1000.) {
+          qstar = q1000_h2o + (q2000_h2o - q1000_h2o) * std::log(pf / 1.E3) / std::log(2.);
+          fac = 0.75 * tau * 86400.;
+        } else {
+          qstar = q3000_h2o;
+          fac = tau * 86400.;
+        }
+      }
+      tab[k] = qstar;
+      tab[npz + k] = fac;
+    }
+    if (tab != c->up_tab_host) {   // a launch that an fv3_group still holds reads the old table: the queues run before it changes
+      if (c->up_tab) {
+        if (int rc = grp_flush_all()) return rc;
+        RT(rtf_sync(c->stream));
+      } else {
+        RT(rt_malloc((void **)&c->up_tab, tab.size() * sizeof(double)));
+      }
+      RT(rtf_h2d(c->up_tab, tab.data(), tab.size() * sizeof(double), c->stream));
+      RT(rtf_sync(c->stream));
+      c->up_tab_host = tab;
+    }
+    qstar_dev = c->up_tab;
+    pfac_dev = c->up_tab + npz;
+  }
+  auto go = [&](auto TBc, auto NWc) -> int {
+    FvUpdatePhys<decltype(TBc)::value, decltype(NWc)::value> kf{
+        g, p->nq, p->ncnst, nw, p->sphum - 1, p->liq_wat - 1, p->rainwat - 1, p->ice_wat - 1, p->snowwat - 1, p->graupel - 1, w_diff - 1, adj,
+        has_qdt ? 1 : 0, relax ? 1 : 0, p->gfs_phys ? 0 : 1, p->dt, p->ptop, p->kappa, p->rdgas, p->rvgas, p->grav, p->cp_air, p->cp_vapor,
+        p->c_liq, p->c_ice, qstar_dev, pfac_dev, t_dt, u_dt, v_dt, q_dt, q, qdiag, delp, pt, delz, ua, va, ps, pe, peln, pk, pkz, u_srf, v_srf};
+    static_assert(decltype(kf)::CH == 256, "col_grid");
+    return launch_p(c, "fv_update_phys", col_grid(g.nx * g.ny), 0, kf);
+  };
+  auto by_nwat = [&](auto TBc) -> int {   // fv_thermodynamics.F90:262-323, :340-402
+    switch (nwc) {
+      case 2: return go(TBc, std::integral_constant<int, 2>{});
+      case 3: return go(TBc, std::integral_constant<int, 3>{});
+      case 4: return go(TBc, std::integral_constant<int, 4>{});
+      case 5: return go(TBc, std::integral_constant<int, 5>{});
+      case 6: return go(TBc, std::integral_constant<int, 6>{});
+      default: return go(TBc, std::integral_constant<int, 0>{});
+    }
+  };
+  if (tb == 0) RT(by_nwat(std::integral_constant<int, 0>{}));
+  else if (tb == 1) RT(by_nwat(std::integral_constant<int, 1>{}));
+  else if (tb == 2) RT(go(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}));
+  else RT(by_nwat(std::integral_constant<int, 3>{}));
   return 0;
 }
 

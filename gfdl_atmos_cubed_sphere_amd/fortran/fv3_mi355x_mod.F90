@@ -27,6 +27,7 @@ module fv3_mi355x_mod
   public :: fv3_neg_adj3, fv3_neg_adj_params
   public :: fv3_fv_subgrid_z, fv3_sg_params, fv3_grid_dwinds, fv3_grid_upload_dwinds, fv3_update_dwinds_phys
   public :: fv3_interpolate_vertical
+  public :: fv3_fv_update_phys, fv3_update_phys_params
 
   type, bind(C) :: fv3_domain
     integer(c_int) :: is, ie, js, je, ng, npx, npy, npz, grid_type
@@ -97,6 +98,16 @@ module fv3_mi355x_mod
     integer(c_int) :: k_bot_full, fv_sg_adj, fv_sg_adj_weak = 0
     real(c_double) :: dt, ptop
     real(c_double) :: rdgas, rvgas, grav, cp_air, cp_vapor, c_liq, c_ice
+  end type
+
+  type, bind(C) :: fv3_update_phys_params   ! fv_update_phys (fv_update_phys.F90:67): the modes, the tracer indices (1-based, 0 = absent),
+    integer(c_int) :: hydrostatic, phys_hydrostatic = 1, gfs_phys = 0    ! the namelist scalars and the caller's constants_mod / gfdl_mp_mod values
+    integer(c_int) :: nq, ncnst, nwat
+    integer(c_int) :: sphum = 0, liq_wat = 0, rainwat = 0, ice_wat = 0, snowwat = 0, graupel = 0, cld_amt = 0, w_diff = 0
+    type(c_ptr) :: adjust_mass = c_null_ptr        ! host address of ncnst integer(c_int) flags (tracer_manager's adjust_mass)
+    real(c_double) :: dt, ptop, tau_h2o = 0.0_c_double
+    type(c_ptr) :: ak = c_null_ptr, bk = c_null_ptr   ! host addresses, npz + 1 each; read only when tau_h2o /= 0
+    real(c_double) :: rdgas, rvgas, grav, cp_air, cp_vapor, kappa, c_liq, c_ice
   end type
 
   type, bind(C) :: fv3_grid_dwinds    ! what update_dwinds_phys reads of the gridstruct on the sphere (fv_grid_utils.F90:3314-3326):
@@ -677,6 +688,16 @@ module fv3_mi355x_mod
       import :: c_int, c_ptr, c_double
       type(c_ptr), value :: ctx, u_dt, v_dt, u, v
       real(c_double), value :: dt
+    end function
+    ! fv_update_phys (fv_update_phys.F90:67-767), the column part: the physics tendencies added to the state, the air mass and the mixing
+    ! ratios adjusted, pe / peln / pk / ps (pkz when hydrostatic) and u_srf / v_srf rebuilt.  q_dt = c_null_ptr: present(q_dt) false; w,
+    ! delz, pkz, qdiag may be c_null_ptr in the mode that does not read them.  The caller goes on with the halo update of u_dt, v_dt as
+    ! two scalars, fv3_update_dwinds_phys and, with gfs_phys, fv3_c2l
+    integer(c_int) function fv3_fv_update_phys(ctx, p, u_dt, v_dt, t_dt, q_dt, delp, pt, q, qdiag, ua, va, w, delz, ps, pe, peln, pk, pkz, &
+                                               u_srf, v_srf) bind(C, name="fv3_fv_update_phys")
+      import :: c_int, c_ptr, fv3_update_phys_params
+      type(c_ptr), value :: ctx, u_dt, v_dt, t_dt, q_dt, delp, pt, q, qdiag, ua, va, w, delz, ps, pe, peln, pk, pkz, u_srf, v_srf
+      type(fv3_update_phys_params), intent(in) :: p
     end function
     ! interpolate_vertical (tools/fv_diagnostics.F90:4910-4948): a3 (km layers) at the pressure plev [Pa] into a2 (is:ie, js:je).
     ! in_ng = 0: a3 on the compute domain, as the reference's argument; in_ng = ng: a state field with its halo, in the place of the

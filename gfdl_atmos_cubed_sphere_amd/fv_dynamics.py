@@ -12,8 +12,9 @@ cld_amt's own remap order (:569-572) follow the reference.  Nudging and the diag
 
 Behind ``fv_dynamics`` the drivers run ``fv_subgrid_z`` once per dt_atmos (driver/SHiELD/atmosphere.F90:599-611, driver/GFDL/
 atmosphere.F90:729-740, driver/solo/fv_phys.F90:315-354): ``fv_subgrid_z`` here is fv_sg_SHiELD and update_dwinds_phys on the device, and
-``atmosphere_step`` = ``step_from_temperature`` + ``fv_subgrid_z`` when fv_sg_adj > 0, the drivers' atmosphere_dynamics.  The rest of
-fv_update_phys (physics tendencies of T and q, the delp adjustment, nudging, del2_phys) is not built.
+``atmosphere_step`` = ``step_from_temperature`` + ``fv_subgrid_z`` when fv_sg_adj > 0, the drivers' atmosphere_dynamics.  After the
+physics the drivers run fv_update_phys (atmosphere_state_update): ``fv_update_phys`` here is the column routine on the device, the halo
+update of u_dt, v_dt, update_dwinds_phys and, with gfs_phys, cubed_to_latlon.  Nudging and del2_phys are not built.
 """
 from __future__ import annotations
 
@@ -200,6 +201,38 @@ class FvDynamics:
         self.step_from_temperature(bdt)
         if self.fv_sg_adj > 0:
             self.fv_subgrid_z(bdt)
+
+    # -- fv_update_phys -------------------------------------------------------------------------------------------
+    def fv_update_phys(self, dt: float, t_dt, q_dt=None, u_dt=None, v_dt=None, phys_hydrostatic: bool = True, gfs_phys: bool = False,
+                       tau_h2o: float = 0.0, adjust_mass=None, w_diff: int = 0):
+        """fv_update_phys (model/fv_update_phys.F90:67-767; atmosphere_state_update of the drivers) on the resident state: the column
+        routine, the halo update of u_dt, v_dt as two scalars (:620-626), update_dwinds_phys (:735) and, with gfs_phys,
+        cubed_to_latlon (:738-742).  t_dt (is:ie, js:je, npz), q_dt (is:ie, js:je, npz, nq) or None, u_dt, v_dt (A x npz) or None
+        (zero wind tendencies): device arrays, or host arrays that are uploaded.  The species are those of the moist dict and cld_amt
+        of the constructor; ps, pe, peln, pk (pkz when hydrostatic) are rebuilt, the bottom winds go to d["u_srf"], d["v_srf"]."""
+        d, ctx, fl = self.dc.d, self.ctx, self.fl
+        hyd = fl.hydrostatic
+        npz = ctx.npz
+        dev = lambda a: ctx.from_host(a) if isinstance(a, (np.ndarray, list, tuple)) else a      # noqa: E731
+        if "u_srf" not in d:
+            d["u_srf"], d["v_srf"] = ctx.zeros("CC"), ctx.zeros("CC")
+        for n, a in (("u_dt", u_dt), ("v_dt", v_dt)):
+            if a is not None:
+                d[n] = dev(a)
+            elif n not in d:
+                d[n] = ctx.zeros("A", npz)
+            else:
+                d[n].zero()
+        species = dict(self.sg_species, cld_amt=self.cld_amt, w_diff=int(w_diff))
+        ctx.fv_update_phys(dt, fl.ptop, hyd, self.nq, self.nq, self.sg_nwat, species, d["u_dt"], d["v_dt"], dev(t_dt),
+                           None if q_dt is None else dev(q_dt), d["delp"], d["pt"], d.get("q"), None, d["ua"], d["va"],
+                           None if hyd else d["w"], None if hyd else d["delz"], d["ps"], d["pe"], d["peln"], d["pk"], d["pkz"] if hyd else None,
+                           d["u_srf"], d["v_srf"], phys_hydrostatic=phys_hydrostatic, gfs_phys=gfs_phys, adjust_mass=adjust_mass,
+                           tau_h2o=tau_h2o, ak=self.ak, bk=self.bk, consts=dict(self.neg_adj_consts, kappa=fl.akap))
+        self.dc.halo.update([(d["u_dt"], "A"), (d["v_dt"], "A")])          # :620-626, :673: two scalars
+        ctx.update_dwinds_phys(dt, d["u_dt"], d["v_dt"], d["u"], d["v"])   # :735
+        if gfs_phys:                                                       # :738-742
+            self.cubed_to_latlon()
 
     # -- neg_adj3 -------------------------------------------------------------------------------------------------
     def _prt_negative(self, when: str):

@@ -37,7 +37,7 @@ EXPORTS = ["fv3_last_error", "fv3_create", "fv3_destroy", "fv3_set_stream", "fv3
            "fv3_set_dp_ref", "fv3_update_dz_c", "fv3_set_condensate", "fv3_set_fast_tau_w", "fv3_set_ray_fast", "fv3_ray_fast", "fv3_mix_dp", "fv3_compute_aam", "fv3_consv_am_apply", "fv3_riem_solver_c", "fv3_update_dz_d", "fv3_riem_solver3",
            "fv3_p_grad_c", "fv3_nh_p_grad", "fv3_split_p_grad", "fv3_grad1_p_update", "fv3_d_sw_inline_q", "fv3_flux_accum", "fv3_fill2d_mass", "fv3_fill2d_apply", "fv3_set_remap_te", "fv3_profile_report_timers", "fv3_prt_maxmin", "fv3_pk3_halo", "fv3_pe_halo", "fv3_geopk", "fv3_zh_from_delz", "fv3_set_ak_bk", "fv3_set_moist", "fv3_lagrangian_to_eulerian",
            "fv3_tracer_2d_prep", "fv3_tracer_2d_scale", "fv3_tracer_2d_step", "fv3_neg_adj3",
-           "fv3_fv_subgrid_z", "fv3_grid_upload_dwinds", "fv3_update_dwinds_phys", "fv3_interpolate_vertical"]
+           "fv3_fv_subgrid_z", "fv3_grid_upload_dwinds", "fv3_update_dwinds_phys", "fv3_interpolate_vertical", "fv3_fv_update_phys"]
 
 
 class Fv3Error(RuntimeError):
@@ -155,6 +155,13 @@ class _SgParams(C.Structure):
     _fields_ = [(n, C.c_int) for n in ["hydrostatic", "nq", "nwat", "sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel",
                                        "k_bot_full", "fv_sg_adj", "fv_sg_adj_weak"]] + [
         (n, C.c_double) for n in ["dt", "ptop", "rdgas", "rvgas", "grav", "cp_air", "cp_vapor", "c_liq", "c_ice"]]
+
+
+class _UpdatePhysParams(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ["hydrostatic", "phys_hydrostatic", "gfs_phys", "nq", "ncnst", "nwat", "sphum", "liq_wat", "rainwat",
+                                       "ice_wat", "snowwat", "graupel", "cld_amt", "w_diff"]] + [("adjust_mass", _ip)] + [
+        (n, C.c_double) for n in ["dt", "ptop", "tau_h2o"]] + [("ak", _dp), ("bk", _dp)] + [
+        (n, C.c_double) for n in ["rdgas", "rvgas", "grav", "cp_air", "cp_vapor", "kappa", "c_liq", "c_ice"]]
 
 
 SG_SPECIES = ("sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel")
@@ -478,6 +485,39 @@ class Context:
             self.upload_dwinds()
         self.lib.check(self.lib.dll.fv3_update_dwinds_phys(self.h, C.c_double(dt), _pp(u_dt), _pp(v_dt), _pp(u), _pp(v)),
                        "fv3_update_dwinds_phys")
+
+    def fv_update_phys(self, dt, ptop, hydrostatic, nq, ncnst, nwat, species, u_dt, v_dt, t_dt, q_dt, delp, pt, q, qdiag, ua, va, w, delz,
+                       ps, pe, peln, pk, pkz, u_srf, v_srf, phys_hydrostatic=True, gfs_phys=False, adjust_mass=None, tau_h2o=0.0, ak=None,
+                       bk=None, consts=None):
+        """fv_update_phys (model/fv_update_phys.F90:67-767), the column part, in place: the physics tendencies t_dt, q_dt (no halo; q_dt may
+        be None), u_dt, v_dt added to the state, the air mass and the mixing ratios adjusted for the change in water, pe / peln / pk / ps
+        (pkz when hydrostatic) and u_srf / v_srf rebuilt.  The caller goes on with the halo update of u_dt, v_dt and update_dwinds_phys.
+        species: {name: 1-based index} of sphum, liq_wat, rainwat, ice_wat, snowwat, graupel, cld_amt, w_diff (absent = 0); adjust_mass:
+        ncnst flags (default: all true); consts: overrides of NEG_ADJ_CONSTS and kappa."""
+        pr = _UpdatePhysParams()
+        pr.hydrostatic, pr.phys_hydrostatic, pr.gfs_phys = int(bool(hydrostatic)), int(bool(phys_hydrostatic)), int(bool(gfs_phys))
+        pr.nq, pr.ncnst, pr.nwat = int(nq), int(ncnst), int(nwat)
+        for n in SG_SPECIES + ("cld_amt", "w_diff"):
+            setattr(pr, n, int((species or {}).get(n, 0)))
+        am = np.ascontiguousarray(np.ones(max(int(ncnst), 1)) if adjust_mass is None else adjust_mass, dtype=np.int32)
+        if am.size < ncnst:
+            raise Fv3Error(f"fv_update_phys: adjust_mass has {am.size} flags for ncnst = {ncnst} tracers")
+        pr.adjust_mass = am.ctypes.data_as(_ip)
+        pr.dt, pr.ptop, pr.tau_h2o = float(dt), float(ptop), float(tau_h2o)
+        keep = [am]
+        for n, a in (("ak", ak), ("bk", bk)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.size != self.npz + 1:
+                    raise Fv3Error(f"fv_update_phys: {n} has {a.size} values for npz + 1 = {self.npz + 1}")
+                keep.append(a)
+                setattr(pr, n, a.ctypes.data_as(_dp))
+        cs = dict(dict(NEG_ADJ_CONSTS, kappa=KAPPA), **(consts or {}))
+        for n in ("rdgas", "rvgas", "grav", "cp_air", "cp_vapor", "kappa", "c_liq", "c_ice"):
+            setattr(pr, n, float(cs[n]))
+        self.lib.check(self.lib.dll.fv3_fv_update_phys(self.h, C.byref(pr), _pp(u_dt), _pp(v_dt), _pp(t_dt), _pp(q_dt), _pp(delp), _pp(pt),
+                                                       _pp(q), _pp(qdiag), _pp(ua), _pp(va), _pp(w), _pp(delz), _pp(ps), _pp(pe), _pp(peln),
+                                                       _pp(pk), _pp(pkz), _pp(u_srf), _pp(v_srf)), "fv3_fv_update_phys")
 
     def interpolate_vertical(self, km, plev, peln, a3, a2, in_ng=0):
         """interpolate_vertical (tools/fv_diagnostics.F90:4910-4948): a2 (is:ie, js:je) = a3 (km layers) at the pressure plev [Pa], linear

@@ -703,6 +703,47 @@ int fv3_grid_upload_dwinds(fv3_ctx *ctx, const fv3_grid_dwinds *g);
  * (bounded_domain: the edge blend is switched off there). */
 int fv3_update_dwinds_phys(fv3_ctx *ctx, double dt, const double *u_dt, const double *v_dt, double *u, double *v);
 
+/* fv3_fv_update_phys -- fv_update_phys, model/fv_update_phys.F90:67-767, what every driver of the reference runs right after the
+ * physics (atmosphere_state_update of driver/SHiELD/atmosphere.F90 and driver/GFDL/atmosphere.F90, driver/solo/fv_phys.F90): the
+ * column part, one launch (six faces of an fv3_group: one).  The sequence of a caller: fv3_fv_update_phys; halo update of u_dt, v_dt
+ * as two scalars (:620-626, :673); fv3_update_dwinds_phys (:735); with gfs_phys, fv3_c2l (:738-742).
+ * Per level, in the reference's order: the tau_h2o relaxation of q_dt(sphum) towards the HALOE profile (:280-317; tau_h2o < 0 wipes
+ * pfull < 100 hPa towards 3e-6, tau_h2o > 0 is the idealized CH4 chemistry above 30 hPa; pfull from get_eta_level(npz, 1e5, ..), :222,
+ * formed on the host from ak, bk); q(m) += dt q_dt(m), m = 1..nq, m /= w_diff (:322-330); ps_dt = 1 + dt sum(q_dt(1:nwat)), delp *=
+ * ps_dt (:335-338); where nwat /= 0, q(m) and qdiag(m) /= ps_dt for every m of 1..ncnst with m /= cld_amt, m /= w_diff and
+ * adjust_mass(m) (:354-371); the temperature (:375-428): hydrostatic, pt += t_dt dt cp_air / cpm with moist_cp; nonhydrostatic with
+ * phys_hydrostatic the same at constant pressure (delz / pt ... * pt); nonhydrostatic with nwat = 0, pt += t_dt dt cp_air / cv_air;
+ * nonhydrostatic with nwat /= 0, moist_cv and the tmax = 330 K limiter, whose excess goes to delz (:412-415, with the pe of before
+ * the call and the delp of after the mass adjustment); ua += dt u_dt, va += dt v_dt unless gfs_phys (:430-437).  Then pe, peln, pk,
+ * ps, pkz (hydrostatic only) from the new delp and u_srf, v_srf (:641-663).  moist_cp / moist_cv are called with t1 present
+ * (fv_thermodynamics.F90:250-404): nwat = 2 takes the GFS case with its three temperature bands; 3, 4, 5, 6 their own; every other
+ * nwat the dry heat capacity.  w_diff counts only when nonhydrostatic (:197-202).  1-based tracer indices, 0 = absent.
+ * q_dt may be NULL: present(q_dt) false, the tracers, the air mass and the mixing ratios stay.
+ * u_dt, v_dt, delp, pt, ua, va: A x npz; q: A x npz x nq; qdiag: A x npz x (ncnst - nq), tracers nq+1..ncnst; ps: A; t_dt (is:ie,
+ * js:je, npz) and q_dt (is:ie, js:je, npz, nq): NO halo; delz, pkz: CC x npz; pe (is-1:ie+1, npz+1, js-1:je+1); peln (is:ie, npz+1,
+ * js:je); pk (is:ie, js:je, npz+1); u_srf, v_srf (is:ie, js:je).  Device pointers; adjust_mass (ncnst flags), ak, bk (npz+1): HOST.
+ * Written, on the compute domain only: q (not w_diff), qdiag, delp, pt, ua, va (unless gfs_phys), delz (nonhydrostatic, unless the
+ * nwat = 0 branch), q_dt(.., sphum) where tau_h2o acts, pe levels 2..npz+1, peln levels 2..npz+1, pk levels 2..npz+1, pkz
+ * (hydrostatic), ps, u_srf, v_srf.  Nothing else: halos, the pe ring, level 1 of pe / peln / pk, u_dt, v_dt, t_dt, w keep their bits.
+ * Refused (status 1 and a message, nothing launched): null fields; npz < 1; nwat < 0; nwat > nq with q_dt; a species index that
+ * the branch needs outside 1..ncnst (sphum, liq_wat for nwat 2..6; rainwat 4..6; ice_wat 3, 5, 6; snowwat 5, 6; graupel 6; sphum
+ * with tau_h2o); w / delz missing when nonhydrostatic; pkz missing when hydrostatic; ak / bk missing with tau_h2o /= 0; ncnst > 64.
+ * Not built: nudging (:505-616); adj_mass_vmr /= 0 and Mw_air (:339-346, :360-367); set_physics_BCs and the regional halo fill
+ * (:224, :682-733); dwind_2d (:665); phys_diag (a caller can difference the state itself); range_check, fv_debug; ts, which the
+ * routine never writes outside nudging. */
+typedef struct fv3_update_phys_params {
+  int hydrostatic, phys_hydrostatic, gfs_phys;
+  int nq, ncnst, nwat;
+  int sphum, liq_wat, rainwat, ice_wat, snowwat, graupel, cld_amt, w_diff;   /* 1-based, 0 = absent */
+  const int *adjust_mass;   /* ncnst flags (tracer_manager's adjust_mass), host */
+  double dt, ptop, tau_h2o;
+  const double *ak, *bk;    /* npz + 1 each, host; read only when tau_h2o /= 0 */
+  double rdgas, rvgas, grav, cp_air, cp_vapor, kappa, c_liq, c_ice;   /* the caller's constants_mod / gfdl_mp values */
+} fv3_update_phys_params;
+int fv3_fv_update_phys(fv3_ctx *ctx, const fv3_update_phys_params *p, const double *u_dt, const double *v_dt, const double *t_dt, double *q_dt,
+                       double *delp, double *pt, double *q, double *qdiag, double *ua, double *va, const double *w, double *delz,
+                       double *ps, double *pe, double *peln, double *pk, double *pkz, double *u_srf, double *v_srf);
+
 /* fv3_interpolate_vertical -- interpolate_vertical, tools/fv_diagnostics.F90:4910-4948 (call sites :2017 the 850 hPa vorticity, :2198 and :2263-2299
  * the relative humidity at 200 hPa and at ten CMIP levels, :2971-2979 condensate at 200 / 500 / 850 hPa, :3522): the field a3 (km layers) at the one pressure plev [Pa], linear in the layer-mean log pressure
  * pm(k) = 0.5 (peln(k) + peln(k+1)) (:4930); at or above pm(1) it is a3(1), at or below pm(km) it is a3(km) (:4933-4936).

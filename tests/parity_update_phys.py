@@ -1,0 +1,532 @@
+"""Check bodies of fv_update_phys -- fv3_fv_update_phys (model/fv_update_phys.F90:67-767), and the sequence behind it -- shared by
+tests/test_update_phys_hostemu.py (CPU) and tests/test_update_phys_gpu.py, and by the contract tests of both: the library against the
+outputs of the reference's compiled Fortran (tests/golden/update_phys_*.npz), against the numpy restatement tests/ref_update_phys.py
+at larger shapes, and properties that need no restatement.  The inputs (tests/update_phys_inputs.py) are conditions: every check
+asserts that the branches it relies on are reached before it compares anything.
+
+Bounds.  Fields without a transcendental (UI.EXACT) are sums, products, quotients, max / min in the reference's order: P.TOL.
+peln, pk, pkz go through include/fv3_math.h, the compiled reference through its libm; measured with
+`python tests/golden/make_update_phys_golden.py --measure` (the library of the CPU harness against the compiled reference, worst of
+the recorded cases, relative RMS / max norm): peln 3.25e-17 / 1.54e-16, pk 1.28e-16 / 9.22e-16, pkz 1.31e-15 / 6.69e-15 (pkz divides a
+difference of powers by a difference of logs: the last-bit differences of its operands are amplified by the thinnest layer's
+pk / (pk(k+1) - pk(k)), about 20 here; pk inherits kappa times the absolute error of peln, which is 11.5 at the surface).  Each bound is ten times the measured relative RMS, and none is above the project's 1e-12."""
+from __future__ import annotations
+
+import functools
+import os
+
+import numpy as np
+
+import parity_common as P
+import ref_fv_sg as SG
+import ref_update_phys as R
+import update_phys_inputs as UI
+from gfdl_atmos_cubed_sphere_amd.lib import Context, Fv3Error
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SHAPES = ((21, 7, 1), (21, 7, 2), (40, 19, 12), (130, 100, 5))
+NWATS = (0, 1, 2, 3, 4, 5, 6)
+OUT = UI.OUT
+BOUND = dict(peln=3.25e-16, pk=1.28e-15, pkz=1.31e-14)
+assert max(BOUND.values()) <= 1.0e-12
+DEVICE = ("u_dt", "v_dt", "t_dt", "q_dt", "delp", "pt", "q", "qdiag", "ua", "va", "w", "delz", "ps", "pe", "peln", "pk", "pkz", "u_srf", "v_srf", "u", "v")
+
+
+@functools.lru_cache(maxsize=None)
+def golden(group):
+    return dict(np.load(os.path.join(HERE, "golden", f"update_phys_{group}.npz")))
+
+
+def params_of(c):
+    """the call's parameters from a case dict (update_phys_inputs.CASES) or keywords of the same names"""
+    km = c["km"]
+    ak, bk = UI.eta_levels(km)
+    return dict(dt=c.get("dt", UI.DT), ptop=c.get("ptop", 300.0), hydrostatic=c["hydrostatic"], phys_hydrostatic=c.get("phys_hydrostatic", True),
+                gfs_phys=c.get("gfs_phys", False), nq=c["nq"], ncnst=c["ncnst"], nwat=c["nwat"], species=UI.species_of(c),
+                adjust_mass=UI.adjust_mass_of(c), has_qdt=c.get("has_qdt", True), tau_h2o=c.get("tau_h2o", 0.0), ak=ak, bk=bk)
+
+
+def call_lib(ctx, d, pr, **over):
+    kw = dict(phys_hydrostatic=pr["phys_hydrostatic"], gfs_phys=pr["gfs_phys"], adjust_mass=pr["adjust_mass"], tau_h2o=pr["tau_h2o"],
+              ak=pr["ak"], bk=pr["bk"], consts=R.CONSTS)
+    kw.update(over)
+    hyd = pr["hydrostatic"]
+    ctx.fv_update_phys(pr["dt"], pr["ptop"], hyd, pr["nq"], pr["ncnst"], pr["nwat"], pr["species"], d["u_dt"], d["v_dt"], d["t_dt"],
+                       d["q_dt"] if pr["has_qdt"] else None, d["delp"], d["pt"], d["q"], d["qdiag"], d["ua"], d["va"], None if hyd else d["w"],
+                       None if hyd else d["delz"], d["ps"], d["pe"], d["peln"], d["pk"], d["pkz"] if hyd else None, d["u_srf"], d["v_srf"], **kw)
+
+
+def nonempty(a):
+    """a zero-size array (no diagnostic tracer, nq = 0) cannot be allocated: one double stands for it, and the library never reads it"""
+    return a if a.size else np.zeros((1,), order="F")
+
+
+def upload(ctx, st):
+    return {n: ctx.from_host(nonempty(st[n])) for n in DEVICE}
+
+
+def download(d, st):
+    return {n: (d[n].download() if st[n].size else st[n].copy()) for n in DEVICE}
+
+
+def run_lib(lib, bd, st, pr, ctx=None, grid=None, whole=False):
+    """fv3_fv_update_phys on a copy of the state (whole: then the periodic halo update of u_dt, v_dt and fv3_update_dwinds_phys, the
+    sequence of the header) -> {field: whole array}"""
+    km = st["pt"].shape[2]
+    own = ctx is None
+    if own:
+        ctx = Context(grid if grid is not None else P.make_grid(bd, False), km, lib=lib)
+    try:
+        d = upload(ctx, st)
+        call_lib(ctx, d, pr)
+        if whole:
+            ctx.halo_periodic_group([(d["u_dt"], "A"), (d["v_dt"], "A")])
+            ctx.update_dwinds_phys(pr["dt"], d["u_dt"], d["v_dt"], d["u"], d["v"])
+        return download(d, st)
+    finally:
+        if own:
+            ctx.close()
+
+
+def run_whole_tile(lib, bd, st, pr):
+    return run_lib(lib, bd, st, pr, whole=True)
+
+
+def run_checker(bd, st, pr, whole=False):
+    """the numpy restatement on a copy of the state -> ({field: whole array}, counts)"""
+    o = {n: st[n].copy(order="F") for n in DEVICE}
+    km = st["pt"].shape[2]
+    cnt = (R.whole_routine_tile if whole else R.fv_update_phys)(bd, km, pr, o)
+    return o, cnt
+
+
+def written_mask(bd, st, pr, name, whole=False):
+    """True where the header says the sequence writes the field"""
+    m = np.zeros(st[name].shape, dtype=bool)
+    r = (bd.is_, bd.ie, bd.js, bd.je)
+    hyd, qdt, nwat = pr["hydrostatic"], pr["has_qdt"], pr["nwat"]
+    sp = pr["species"]
+    w_diff = 0 if hyd else sp.get("w_diff", 0)
+    if name in ("u", "v"):
+        if whole:
+            (bd.view(m, "U", bd.is_, bd.ie, bd.js, bd.je + 1) if name == "u" else bd.view(m, "V", bd.is_, bd.ie + 1, bd.js, bd.je))[...] = True
+    elif name == "q":
+        if qdt:
+            bd.view(m, "A", *r)[...] = True
+            if w_diff:
+                m[..., w_diff - 1] = False
+    elif name == "qdiag":
+        if qdt and nwat != 0:
+            for k in range(pr["nq"], pr["ncnst"]):
+                if pr["adjust_mass"][k] and k + 1 not in (sp.get("cld_amt", 0), w_diff):
+                    bd.view(m, "A", *r)[..., k - pr["nq"]] = True
+    elif name == "delp":
+        if qdt:
+            bd.view(m, "A", *r)[...] = True
+    elif name in ("ua", "va"):
+        if not pr["gfs_phys"]:
+            bd.view(m, "A", *r)[...] = True
+    elif name in ("pt", "ps"):
+        bd.view(m, "A", *r)[...] = True
+    elif name == "q_dt":
+        if qdt and pr["tau_h2o"] != 0.0:
+            _, p_fac = R.tau_table(st["pt"].shape[2], pr["tau_h2o"], pr["ak"], pr["bk"], R.CONSTS["kappa"])
+            m[:, :, p_fac != 0.0, sp["sphum"] - 1] = True
+    elif name == "delz":
+        if not hyd and (pr["phys_hydrostatic"] or nwat != 0):
+            m[...] = True
+    elif name == "pkz":
+        if hyd:
+            m[...] = True
+    elif name == "pe":
+        m[1:-1, 1:, 1:-1] = True
+    elif name == "peln":
+        m[:, 1:, :] = True
+    elif name == "pk":
+        m[:, :, 1:] = True
+    elif name in ("u_srf", "v_srf"):
+        m[...] = True
+    return m
+
+
+def compare(bd, st, got, ref, pr, whole=False):
+    """every written field at its bound on the range the header gives; everything else, the pure inputs included, keeps its bits.
+    -> the worst relative RMS of the fields without a transcendental"""
+    worst = 0.0
+    for n in DEVICE:
+        if not st[n].size:
+            continue
+        m = written_mask(bd, st, pr, n, whole)
+        if n in ("u_dt", "v_dt") and whole:      # the halo update writes their halo
+            m = np.ones(st[n].shape, dtype=bool)
+            bd.view(m, "A", bd.is_, bd.ie, bd.js, bd.je)[...] = False
+            assert np.array_equal(got[n][~m].view(np.uint64), st[n][~m].view(np.uint64)), f"{n}: written on the compute domain"
+            continue
+        if m.any():
+            e = P.assert_close(n, got[n][m], ref[n][m], BOUND.get(n, P.TOL))
+            if n not in BOUND:
+                worst = max(worst, e)
+        assert np.array_equal(got[n][~m].view(np.uint64), st[n][~m].view(np.uint64)), f"{n}: written outside what the header names"
+    return worst
+
+
+def bit_identical(bd, st, got, ref, pr, whole=False):
+    out = {}
+    for n in OUT:
+        m = written_mask(bd, st, pr, n, whole)
+        if m.any():
+            out[n] = bool(np.array_equal(got[n][m], ref[n][m]))
+    return out
+
+
+def assert_conditions(pr, cnt, st=None, ref=None):
+    """the branches a comparison relies on are reached: each t1 band for nwat = 2, the limiter hit and not hit in the moist
+    constant-volume branch, the brackets of tau_h2o when the level table has them all (km = 8)"""
+    moist_heat = pr["hydrostatic"] or pr["phys_hydrostatic"] or pr["nwat"] != 0
+    if pr["nwat"] == 2 and moist_heat:
+        for n in ("band_warm", "band_cold", "band_mixed"):
+            assert cnt[n] > 0, (n, cnt)
+    if not pr["hydrostatic"] and not pr["phys_hydrostatic"] and pr["nwat"] != 0:
+        assert cnt["limited"] > 0 and cnt["not_limited"] > 0, cnt
+    if pr["has_qdt"] and pr["tau_h2o"] > 0.0 and len(pr["ak"]) == 9:
+        for n in ("tau_lt1", "tau_lt7", "tau_lt100", "tau_lt1000", "tau_lt2000", "tau_lt3000", "tau_none"):
+            assert cnt[n] > 0, (n, cnt)
+    if pr["has_qdt"] and pr["tau_h2o"] < 0.0 and len(pr["ak"]) == 9:
+        assert cnt["tau_wipe"] > 0 and cnt["tau_none"] > 0, cnt
+
+
+# ---- the recorded outputs of the reference's compiled Fortran ----------------------------------------------------------------------
+def golden_case(name):
+    """-> (case, bd, inputs, the reference's outputs as whole arrays: the inputs with the recorded ranges laid over them)"""
+    c = UI.CASES[name]
+    bd, st = UI.case_inputs(name)
+    g = golden(c["group"])
+    assert str(g[f"{name}|sha"]) == UI.checksum(st), f"{name}: the inputs formed from the seed are not those the golden was recorded with"
+    ref = {n: st[n].copy(order="F") for n in DEVICE}
+    for n in OUT:
+        key = f"{name}|out|{n}"
+        if key in g:
+            _written_range(bd, n, ref[n])[...] = g[key]
+    return c, bd, st, ref
+
+
+def _written_range(bd, name, a):
+    """the range a golden keeps of a field (make_update_phys_golden.written)"""
+    if name == "u":
+        return bd.view(a, "U", bd.is_, bd.ie, bd.js, bd.je + 1)
+    if name == "v":
+        return bd.view(a, "V", bd.is_, bd.ie + 1, bd.js, bd.je)
+    if name == "pe":
+        return a[1:-1, :, 1:-1]
+    if name in ("q", "qdiag", "delp", "pt", "ua", "va", "ps"):
+        return bd.view(a, "A", bd.is_, bd.ie, bd.js, bd.je)
+    return a
+
+
+def check_checker_against_golden(name):
+    """the numpy restatement against the compiled reference: the fields without a transcendental bit for bit, peln / pk / pkz at
+    their bounds (numpy's log and exp are not the compiled reference's); and the recorded case reaches the branches it is there for"""
+    c, bd, st, ref = golden_case(name)
+    pr = params_of(c)
+    got, cnt = run_checker(bd, st, pr, whole=True)
+    assert_conditions(pr, cnt)
+    for n in OUT:
+        if n in BOUND:
+            m = written_mask(bd, st, pr, n, True)
+            if m.any():
+                P.assert_close(n, got[n][m], ref[n][m], BOUND[n])
+            continue
+        assert np.array_equal(got[n].view(np.uint64), ref[n].view(np.uint64)), f"{name}: {n} of the restatement is not the reference's, max diff {np.max(np.abs(got[n] - ref[n])):.3e}"
+    # the mask of what the header calls written is the reference's: nothing recorded lies outside it
+    for n in OUT:
+        m = written_mask(bd, st, pr, n, True)
+        assert np.array_equal(ref[n][~m].view(np.uint64), st[n][~m].view(np.uint64)), f"{name}: the reference writes {n} where the header says nothing is written"
+    return cnt
+
+
+def check_lib_against_golden(lib, name):
+    """the library's whole sequence against the recorded outputs with nothing in between
+    -> (worst relative RMS of the exact fields, {field: bit-identical}, {field: relative RMS of peln / pk / pkz})"""
+    c, bd, st, ref = golden_case(name)
+    pr = params_of(c)
+    got = run_whole_tile(lib, bd, st, pr)
+    trans = {}
+    for n in BOUND:
+        m = written_mask(bd, st, pr, n, True)
+        if m.any():
+            trans[n] = (float(P.rel_rms(got[n][m], ref[n][m])), float(np.max(np.abs(got[n][m] - ref[n][m])) / np.max(np.abs(ref[n][m]))))
+    bits = bit_identical(bd, st, got, ref, pr, True)
+    print(name, "bit-identical:", bits, "rel-rms / max norm:", trans)
+    return compare(bd, st, got, ref, pr, whole=True), bits, trans
+
+
+# ---- the restatement at larger shapes ----------------------------------------------------------------------------------------------
+def generic_case(shape, hydrostatic, phys_hydrostatic, nwat, has_qdt=True, gfs_phys=False, tau_h2o=0.0, seed=901):
+    nx, ny, km = shape
+    nq, ncnst = 8, 9
+    c = dict(km=km, hydrostatic=hydrostatic, phys_hydrostatic=phys_hydrostatic, nwat=nwat, has_qdt=has_qdt, gfs_phys=gfs_phys, tau_h2o=tau_h2o, nq=nq,
+             ncnst=ncnst, cld_amt=7, w_diff=8, adjust_off=(8,))
+    pr = params_of(c)
+    bd, st = UI.state(nx, ny, km, nq, ncnst, nwat, seed + 7 * nwat + int(hydrostatic) + 2 * int(phys_hydrostatic))
+    return pr, bd, st
+
+
+def check_against_checker(lib, shape, hydrostatic, phys_hydrostatic, nwat, **kw):
+    pr, bd, st = generic_case(shape, hydrostatic, phys_hydrostatic, nwat, **kw)
+    ref, cnt = run_checker(bd, st, pr)
+    if st["pt"].size >= 2000:
+        assert_conditions(pr, cnt)
+    return compare(bd, st, run_lib(lib, bd, st, pr), ref, pr)
+
+
+# ---- properties that need no restatement -------------------------------------------------------------------------------------------
+def check_zero_tendencies(lib, shape, hydrostatic, phys_hydrostatic, nwat=6):
+    """all tendencies zero: every field except pe, peln, pk, pkz, ps, u_srf, v_srf keeps its bits; delz under phys_hydrostatic goes
+    through (delz / pt) * pt and stays within 2 ulp (one rounding each of the quotient and the product)"""
+    nx, ny, km = shape
+    pr = params_of(dict(km=km, hydrostatic=hydrostatic, phys_hydrostatic=phys_hydrostatic, nwat=nwat, nq=8, ncnst=9, cld_amt=7, w_diff=8))
+    bd, st = UI.state(nx, ny, km, 8, 9, nwat, seed=911, zero_tendencies=True)
+    st["pt"] = np.minimum(st["pt"], 320.0)
+    got = run_lib(lib, bd, st, pr)
+    for n in DEVICE:
+        if n in ("pe", "peln", "pk", "pkz", "ps", "u_srf", "v_srf"):
+            continue
+        if n == "delz" and not hydrostatic and phys_hydrostatic:
+            ulp = np.spacing(np.abs(st[n]))
+            assert np.all(np.abs(got[n] - st[n]) <= 2.0 * ulp), "delz moved by more than 2 ulp"
+            continue
+        assert np.array_equal(got[n].view(np.uint64), st[n].view(np.uint64)), f"{n}: changed by zero tendencies"
+    r = (bd.is_, bd.ie, bd.js, bd.je)
+    A = lambda a: bd.view(a, "A", *r)      # noqa: E731
+    assert np.array_equal(got["u_srf"], A(st["ua"])[:, :, -1]) and np.array_equal(got["v_srf"], A(st["va"])[:, :, -1])
+    pe = got["pe"][1:-1, :, 1:-1]
+    assert np.array_equal(A(got["ps"]), pe[:, -1, :])
+    for k in range(km):
+        assert np.array_equal(pe[:, k + 1, :], pe[:, k, :] + A(st["delp"])[:, :, k])
+
+
+def check_dry_mass(lib, shape, hydrostatic, nwat=6):
+    """every water species with adjust_mass: delp (1 - sum q(1:nwat)) is what the adjustment conserves.
+    With S = dt sum(q_dt), ps_dt = 1 + S: delp' = delp ps_dt, q' = (q + dt q_dt) / ps_dt, so delp' (1 - sum q') = delp (ps_dt - sum q - S)
+    = delp (1 - sum q) exactly.  In floating point: each of the nwat species carries 3 roundings (the product dt q_dt, the sum, the
+    quotient), the sum over the species nwat more, S and ps_dt nwat + 2, delp' one, and the final 1 - sum, product two on either
+    side: 5 nwat + 7 roundings of relative size eps on quantities bounded by delp -- the bound, relative to delp"""
+    nx, ny, km = shape
+    pr = params_of(dict(km=km, hydrostatic=hydrostatic, phys_hydrostatic=True, nwat=nwat, nq=8, ncnst=9, cld_amt=7, w_diff=8))
+    bd, st = UI.state(nx, ny, km, 8, 9, nwat, seed=921)
+    got = run_lib(lib, bd, st, pr)
+    r = (bd.is_, bd.ie, bd.js, bd.je)
+    A = lambda a: bd.view(a, "A", *r)      # noqa: E731
+    dry = lambda s: A(s["delp"]) * (1.0 - A(s["q"])[..., :nwat].sum(axis=-1))      # noqa: E731
+    assert np.any(A(got["delp"]) != A(st["delp"]))
+    err = np.abs(dry(got) - dry(st)) / A(st["delp"])
+    bound = (5 * nwat + 7) * np.finfo(float).eps
+    assert err.max() <= bound, (float(err.max()), bound)
+    return float(err.max())
+
+
+# ---- the memory contract -----------------------------------------------------------------------------------------------------------
+def check_contract(lib, shape, hydrostatic):
+    """meant to run under memory_contract.run_case (every device array between guard bands, FV3_MI355X_POISON=1): the pure outputs
+    (ps, u_srf, v_srf, pkz, the levels 2.. of peln and pk) prefilled with the pattern; halos and everything the header calls unwritten
+    bit-unchanged (compare); a call after another kind of call in the same context gives the bits of a fresh context"""
+    import memory_contract as MC
+    pr, bd, st = generic_case(shape, hydrostatic, False, 6, tau_h2o=2.0, seed=931)
+    for n in ("ps", "u_srf", "v_srf", "pkz"):
+        st[n] = MC.pattern_array(st[n].shape)
+    for n, keep in (("peln", (slice(None), 0, slice(None))), ("pk", (slice(None), slice(None), 0))):
+        a = MC.pattern_array(st[n].shape)
+        a[keep] = st[n][keep]
+        st[n] = a
+    ref, cnt = run_checker(bd, st, pr)
+    assert_conditions(pr, cnt)
+    fresh = run_lib(lib, bd, st, pr, whole=True)
+    refw, _ = run_checker(bd, st, pr, whole=True)
+    worst = compare(bd, st, fresh, refw, pr, whole=True)
+    km = shape[2]
+    ctx = Context(P.make_grid(bd, False), km, lib=lib)
+    try:
+        other, _, st2 = generic_case(shape, not hydrostatic, True, 3, has_qdt=False, seed=933)
+        call_lib(ctx, upload(ctx, st2), other)
+        other, _, st2 = generic_case(shape, hydrostatic, False, 2, tau_h2o=-1.0, seed=935)      # another tau_h2o table in the same context
+        call_lib(ctx, upload(ctx, st2), other)
+        again = run_lib(lib, bd, st, pr, ctx=ctx, whole=True)
+    finally:
+        ctx.close()
+    for n in DEVICE:
+        assert np.array_equal(again[n].view(np.uint64), fresh[n].view(np.uint64)), f"{n}: a call after another call differs from a fresh context"
+    return worst
+
+
+# ---- refusals ----------------------------------------------------------------------------------------------------------------------
+def check_refusals(lib):
+    pr, bd, st = generic_case((12, 9, 6), False, False, 6, tau_h2o=2.0, seed=941)
+    ctx = Context(P.make_grid(bd, False), 6, lib=lib)
+    try:
+        d = upload(ctx, st)
+
+        def refused(match, p=pr, drop=(), **over):
+            dd = dict(d, **{n: None for n in drop})
+            try:
+                call_lib(ctx, dd, p, **over)
+            except Fv3Error as e:
+                assert match in str(e), (match, str(e))
+            else:
+                raise AssertionError(f"fv3_fv_update_phys took a call that must be refused ({match})")
+
+        for n in ("u_dt", "v_dt", "t_dt", "delp", "pt", "ua", "va", "ps", "pe", "peln", "pk", "u_srf", "v_srf", "q", "qdiag"):
+            refused("null", drop=(n,))
+        refused("w and delz", drop=("delz",))
+        refused("w and delz", drop=("w",))
+        refused("pkz", dict(pr, hydrostatic=True), drop=("pkz",))
+        refused("nwat", dict(pr, nwat=-1))
+        refused("nwat", dict(pr, nwat=9))      # > nq with q_dt
+        six = pr["species"]
+        for name in UI.SPECIES:
+            refused(name, dict(pr, species=dict(six, **{name: 0})))
+        refused("graupel", dict(pr, species=dict(six, graupel=10)))
+        refused("ice_wat", dict(pr, nwat=3, species=dict(sphum=1, liq_wat=2)))
+        refused("rainwat", dict(pr, nwat=4, species=dict(sphum=1, liq_wat=2)))
+        refused("snowwat", dict(pr, nwat=5, species=dict(sphum=1, liq_wat=2, rainwat=3, ice_wat=4)))
+        refused("liq_wat", dict(pr, nwat=2, species=dict(sphum=1)))
+        refused("sphum", dict(pr, nwat=0, species={}))      # tau_h2o relaxes q_dt(sphum)
+        refused("ak and bk", ak=None)
+        refused("ak and bk", bk=None)
+        got = download(d, st)
+        for n in DEVICE:
+            assert np.array_equal(got[n].view(np.uint64), st[n].view(np.uint64)), f"{n}: a refused call wrote"
+        # npz < 1 cannot be reached: fv3_create refuses such a domain.  What is NOT refused: nwat > nq without q_dt (nothing is summed),
+        # nwat = 1 and 7 (the dry heat capacity of `case default`), the species that the branch does not read left out
+        call_lib(ctx, upload(ctx, st), dict(pr, nwat=9, has_qdt=False, species=dict(sphum=1)))
+        call_lib(ctx, upload(ctx, st), dict(pr, nwat=1, tau_h2o=0.0, species={}))
+        call_lib(ctx, upload(ctx, st), dict(pr, nwat=7, tau_h2o=0.0, species={}))
+    finally:
+        ctx.close()
+
+
+# ---- six faces as one group ------------------------------------------------------------------------------------------------------
+def check_six_faces(lib, npx=13, npz=6, hydrostatic=False):
+    """the six faces as one fv3_group: the bits of face-by-face runs, and ONE merged launch for the column kernel"""
+    import cubed_common as CC
+    from gfdl_atmos_cubed_sphere_amd.cubed_dyn import MultiContext
+    cs, gs = CC.sphere(npx)
+    n = npx - 1
+    sts = []
+    for t in range(6):
+        pr, bd, st = generic_case((n, n, npz), hydrostatic, False, 6, seed=950 + t)
+        sts.append(st)
+    bd = gs[0].bd
+    alone = [run_lib(lib, bd, st, pr, grid=gs[t]) for t, st in enumerate(sts)]
+    for t, st in enumerate(sts):
+        ref, cnt = run_checker(bd, st, pr)
+        compare(bd, st, alone[t], ref, pr)
+    mctx = MultiContext([Context(g, npz, lib=lib) for g in gs], group=True)
+    try:
+        assert mctx.group is not None
+        d = {name: mctx.from_host([nonempty(st[name]) for st in sts]) for name in DEVICE}
+        mctx.flush()
+        mctx.group.stats()
+        call_lib(mctx, d, pr)
+        mctx.flush()
+        merged, single = mctx.group.stats()
+        assert merged == 1 and single == 0, f"fv_update_phys of six faces: {merged} merged launches, {single} single ones"
+        for name in DEVICE:
+            got = d[name].download()
+            for t in range(6):
+                assert np.array_equal(got[t].view(np.uint64), alone[t][name].view(np.uint64)), f"face {t + 1} {name}"
+    finally:
+        mctx.close()
+
+
+# ---- the Python host: FvDynamics.fv_update_phys ------------------------------------------------------------------------------------
+def check_host(lib, where, gfs_phys=False):
+    """FvDynamics.fv_update_phys on the state a step of parity_negadj.run_tile / run_sphere leaves (24 x 16 x 10 on the doubly periodic
+    tile, C12 L8, moist, nwat = 6, nq = 7, nonhydrostatic) against the restatement of the column routine, a real exchange of u_dt,
+    v_dt as two scalars and the restatement of update_dwinds_phys; with gfs_phys, ua / va against the run's own cubed_to_latlon"""
+    import gfdl_atmos_cubed_sphere_amd.fv_dynamics as M
+    import parity_negadj as NA
+    import parity_remap as PR
+    import parity_subgrid as PS
+    from gfdl_atmos_cubed_sphere_amd.layout import periodic_fill
+    orig, kept = M.FvDynamics, {}
+    fields = ("u", "v", "w", "delp", "pt", "ua", "va", "q", "delz", "pe", "peln", "pk", "ps")
+
+    class UpFvDynamics(orig):
+        def __init__(self, *a, **kw):
+            super().__init__(*a, **kw)
+            if where == "sphere":      # the tests' gridstructs are the oracle's: what update_dwinds_phys reads comes from there as well
+                import cubed_common as CC
+                cs, _ = CC.sphere(self.ctx.grid.npx)
+                for t, c in enumerate(self.ctx.ctxs):
+                    c.upload_dwinds(PS.oracle_dwinds_geom(cs, t))
+
+        def step_from_temperature(self, bdt):
+            super().step_from_temperature(bdt)
+            d, bd, npz = self.dc.d, self.ctx.bd, self.ctx.npz
+            dl = lambda n: NA._faces(d[n].download())      # noqa: E731
+            before = {n: [a.copy(order="F") for a in dl(n)] for n in fields}
+            nf = len(before["pt"])
+            tend = []
+            for t in range(nf):
+                rng = np.random.default_rng(960 + t)
+                q = bd.view(before["q"][t], "A", bd.is_, bd.ie, bd.js, bd.je)
+                f = lambda s: np.asfortranarray(1.0e-3 * rng.standard_normal(s))      # noqa: E731
+                tend.append(dict(t_dt=f((bd.nx, bd.ny, npz)), q_dt=np.asfortranarray(q * rng.uniform(-0.3, 0.3, q.shape) / bdt),
+                                 u_dt=f(bd.shape("A", npz)), v_dt=f(bd.shape("A", npz))))
+            pick = (lambda n: tend[0][n]) if nf == 1 else (lambda n: [x[n] for x in tend])
+            self.fv_update_phys(bdt, pick("t_dt"), pick("q_dt"), pick("u_dt"), pick("v_dt"), phys_hydrostatic=False, gfs_phys=gfs_phys)
+            kept.update(before=before, tend=tend, bdt=bdt, consts=dict(self.neg_adj_consts, kappa=self.fl.akap), ptop=self.fl.ptop,
+                        after={n: dl(n) for n in fields + ("u_srf", "v_srf")}, ak=self.ak, bk=self.bk, c2l=self.c2l_ord)
+
+    M.FvDynamics = UpFvDynamics
+    try:
+        base = (NA.run_tile if where == "tile" else NA.run_sphere)(lib)
+    finally:
+        M.FvDynamics = orig
+    bd = base["bd"]
+    before, after, tend = kept["before"], kept["after"], kept["tend"]
+    nf = len(before["pt"])
+    npz = before["pt"][0].shape[2]
+    sp = {n: PR.MOIST6[n] for n in UI.SPECIES if n != "sphum"}
+    sp["sphum"] = 1
+    nq = before["q"][0].shape[3]
+    pr = dict(dt=kept["bdt"], ptop=kept["ptop"], hydrostatic=False, phys_hydrostatic=False, gfs_phys=gfs_phys, nq=nq, ncnst=nq, nwat=PR.MOIST6["nwat"],
+              species=sp, adjust_mass=np.ones(nq, dtype=np.int32), has_qdt=True, tau_h2o=0.0, ak=kept["ak"], bk=kept["bk"])
+    ref = []
+    for t in range(nf):
+        s = {n: before[n][t].copy(order="F") for n in fields}
+        s.update({n: tend[t][n].copy(order="F") for n in tend[t]})
+        s.update(qdiag=np.zeros(bd.shape("A", npz) + (0,), order="F"), pkz=np.zeros((bd.nx, bd.ny, npz), order="F"),
+                 u_srf=np.zeros((bd.nx, bd.ny), order="F"), v_srf=np.zeros((bd.nx, bd.ny), order="F"))
+        R.fv_update_phys(bd, npz, pr, s, consts=kept["consts"])
+        ref.append(s)
+    if where == "tile":
+        for n in ("u_dt", "v_dt"):
+            periodic_fill(bd, ref[0][n], "A")
+        geoms = [None]
+    else:
+        import cubed_common as CC
+        cs, _ = CC.sphere(base["gs"][0].npx)
+        CC.exchange(cs, ref, ("u_dt", "v_dt"), "A")
+        geoms = [PS.oracle_dwinds_geom(cs, t) for t in range(6)]
+    worst = 0.0
+    r = (bd.is_, bd.ie, bd.js, bd.je)
+    for t in range(nf):
+        g = base["g"] if where == "tile" else base["gs"][t]
+        SG.update_dwinds_phys(bd, g.npx, g.npy, g.grid_type, kept["bdt"], ref[t]["u_dt"], ref[t]["v_dt"], ref[t]["u"], ref[t]["v"], geoms[t])
+        rows = [("u", "U", (bd.is_, bd.ie, bd.js, bd.je + 1)), ("v", "V", (bd.is_, bd.ie + 1, bd.js, bd.je)), ("pt", "A", r), ("w", "A", r), ("q", "A", r),
+                ("delp", "A", r), ("ps", "A", r)]
+        if not gfs_phys:
+            rows += [("ua", "A", r), ("va", "A", r)]
+        for n, kind, rg in rows:
+            a, b = bd.view(after[n][t], kind, *rg), bd.view(ref[t][n], kind, *rg)
+            assert np.any(b != bd.view(before[n][t], kind, *rg)) or n == "w", n
+            worst = max(worst, P.assert_close(f"face {t + 1} {n}", a, b, P.TOL))
+        worst = max(worst, P.assert_close(f"face {t + 1} delz", after["delz"][t], ref[t]["delz"], P.TOL))
+        P.assert_close(f"face {t + 1} pe", after["pe"][t][1:-1, :, 1:-1], ref[t]["pe"][1:-1, :, 1:-1], P.TOL)
+        for n in ("peln", "pk"):
+            P.assert_close(f"face {t + 1} {n}", after[n][t], ref[t][n], BOUND[n])
+        if gfs_phys:      # ua, va are cubed_to_latlon of the updated D-grid winds, not ua + dt u_dt
+            ua0, ua1 = bd.view(before["ua"][t], "A", *r), bd.view(after["ua"][t], "A", *r)
+            assert np.any(ua1 != ua0) and np.any(ua1 != ua0 + kept["bdt"] * bd.view(tend[t]["u_dt"], "A", *r))
+    return worst

@@ -1,0 +1,173 @@
+"""Seeded inputs of the fv_update_phys tests, shared by the recorder of the reference goldens (tests/golden/make_update_phys_golden.py),
+the numpy restatement's own test and the library tests.  Pure numpy.
+
+The columns: sigma = linspace(0, 1, km+1)^1.5 over ptop .. ps, ps uniform in 9.5e4 .. 1.02e5; T = 210 .. 300 K rising with pressure
++ 3 K N(0, 1); qv <= 1.5e-2 (pm / 1e5)^3, condensates <= 2e-4, passive tracers in 0 .. 1, two of them partly negative; delz
+hydrostatic from T_v; winds 10 m/s N(0, 1).  The tendencies over dt = 225 s: t_dt 2e-3 K/s N(0, 1), q_dt so that a water species
+changes by up to 30 % (vapour) and 50 % (condensates) -- ps_dt differs from 1 by up to 5e-3 --, u_dt, v_dt 1e-3 m/s2 N(0, 1) with every halo cell random (the halo
+update has to replace them).  What the routine overwrites without reading (ps, u_srf, v_srf, pkz, levels 2.. of peln and pk) starts
+as noise.  pe(2..) of the input is NOT the running sum of delp but 0.3 % off it: the tmax limiter (:412-415) reads the pe of before
+the call, and a routine that read the rebuilt one would differ in the sixth digit of delz.
+
+Planted, each in cells of its own, so that the recorded cases and the larger shapes reach every branch:
+ - T in the three bands of moist_cp / moist_cv's t1 case (nwat = 2): above tice, below tice - 15 K, between;
+ - t_dt that carries T beyond tmax = 330 K (by 5 .. 600 K) in a sixteenth of the cells; every other cell ends 20 K and more below it.
+"""
+from __future__ import annotations
+
+import hashlib
+
+import numpy as np
+
+from gfdl_atmos_cubed_sphere_amd.layout import Bounds
+
+RDGAS, RVGAS, GRAV, KAPPA = 287.04, 461.50, 9.80, 2.0 / 7.0
+CP_AIR = RDGAS / KAPPA
+ZVIR = RVGAS / RDGAS - 1.0
+DT = 225.0
+TICE, TMAX = 273.16, 330.0
+SPECIES = ("sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel")
+# species indices (1-based) per nwat, as a field_table of that microphysics orders them
+SPECIES_OF = {
+    0: dict(sphum=1),
+    1: dict(sphum=1),
+    2: dict(sphum=1, liq_wat=2),
+    3: dict(sphum=1, liq_wat=2, ice_wat=3),
+    4: dict(sphum=1, liq_wat=2, rainwat=3),
+    5: dict(sphum=1, liq_wat=2, rainwat=3, ice_wat=4, snowwat=5),
+    6: dict(sphum=1, liq_wat=2, rainwat=3, ice_wat=4, snowwat=5, graupel=6),
+}
+# the fields the routine may write, and the kind of each (layout.Bounds kinds; None: a layout of its own)
+OUT = ("q", "q_dt", "qdiag", "delp", "pt", "delz", "ua", "va", "u", "v", "pe", "peln", "pk", "pkz", "ps", "u_srf", "v_srf")
+IN_ONLY = ("t_dt", "u_dt", "v_dt", "w")
+EXACT = ("q", "q_dt", "qdiag", "delp", "pt", "delz", "ua", "va", "u", "v", "pe", "ps", "u_srf", "v_srf")   # no transcendental
+TRANSCENDENTAL = ("peln", "pk", "pkz")
+
+
+def eta_levels(km):
+    """ak, bk (km + 1 each).  km = 8: pfull of get_eta_level(km, 1e5, ..) = 0.43, 2.6, 29, 313, 1233, 2176, 13685, 65481 Pa -- one
+    level in every bracket of fv_update_phys.F90:292-310 and two below 3000 Pa; two beyond 100 hPa for tau_h2o < 0.  Any other km:
+    interfaces spaced geometrically from 0.2 Pa to 1e5 Pa."""
+    if km == 8:
+        ph = np.array([0.2, 0.8, 6.0, 80.0, 800.0, 1800.0, 2600.0, 40000.0, 100000.0])
+        bk = np.array([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.35, 1.0])
+    else:
+        ph = np.geomspace(0.2, 1.0e5, km + 1)
+        bk = np.where(ph > 5.0e3, (ph - 5.0e3) / (1.0e5 - 5.0e3), 0.0)
+    return ph - bk * 1.0e5, bk
+
+
+def state(nx, ny, km, nq, ncnst, nwat, seed, ptop=300.0, zero_tendencies=False):
+    """-> (bd, dict of arrays in the library's layouts)"""
+    bd = Bounds(1, nx, 1, ny)
+    ng = bd.ng
+    rng = np.random.default_rng(seed)
+    sig = np.linspace(0.0, 1.0, km + 1) ** 1.5
+    ps = rng.uniform(9.5e4, 1.02e5, (nx + 2, ny + 2))
+    pe3 = ptop * (1.0 - sig)[None, None, :] + sig[None, None, :] * ps[:, :, None]      # (nx+2, ny+2, km+1)
+    pec = pe3[1:-1, 1:-1, :]
+    peln_c = np.log(pec)
+    dpc = pec[:, :, 1:] - pec[:, :, :-1]
+    dl = peln_c[:, :, 1:] - peln_c[:, :, :-1]
+    pm = dpc / dl
+    T = 210.0 + 90.0 * (pm / 1.0e5) + 3.0 * rng.standard_normal((nx, ny, km))
+    sp = SPECIES_OF[nwat]
+    q = rng.uniform(0.0, 1.0, (nx, ny, km, max(nq, 1)))
+    q[..., sp["sphum"] - 1] *= 1.5e-2 * (pm / 1.0e5) ** 3
+    for n in SPECIES[1:]:
+        if n in sp:
+            q[..., sp[n] - 1] *= 2.0e-4
+    if nq > len(sp) + 1:
+        q[..., -2:] -= 0.3
+    q = q[..., :nq]
+    qdiag = rng.uniform(0.0, 1.0, (nx, ny, km, ncnst - nq))
+    qv = q[..., 0] if nq else np.zeros_like(T)
+    # ---- the tendencies
+    t_dt = 2.0e-3 * rng.standard_normal((nx, ny, km))
+    q_dt = q * rng.uniform(-0.5, 0.5, q.shape) / DT
+    if nq:
+        q_dt[..., 0] *= 0.6
+    cell = rng.permutation(nx * ny * km)
+    ci, cj, ck = np.unravel_index(cell, (nx, ny, km))
+    n3 = max(3, (nx * ny * km) // 16)
+    for m in range(n3):                                             # the three bands of the t1 case
+        T[ci[m], cj[m], ck[m]] = (TICE + 5.0 + m % 7, TICE - 20.0 - m % 7, TICE - 1.0 - 2.0 * (m % 7))[m % 3]
+    T = np.minimum(T, TMAX - 25.0)
+    hot = slice(n3, 2 * n3)                                         # beyond tmax after the update, in every temperature branch
+    excess = np.array([5.0, 15.0, 80.0, 600.0])[np.arange(n3) % 4]
+    t_dt[ci[hot], cj[hot], ck[hot]] = (TMAX + excess - T[ci[hot], cj[hot], ck[hot]]) / DT * 1.5
+    delz = -RDGAS * T * (1.0 + ZVIR * qv) * dl / GRAV
+
+    def halo(c, kind="A"):
+        a = np.asfortranarray(rng.uniform(-1.0, 1.0, bd.shape(kind, km) + c.shape[3:]))
+        a[ng:ng + nx, ng:ng + ny] = c
+        return a
+    noise = lambda *s: np.asfortranarray(rng.uniform(1.0, 2.0, s))      # noqa: E731
+    pe = np.asfortranarray(np.transpose(pe3, (0, 2, 1)))                                        # (nx+2, km+1, ny+2)
+    pe[:, 1:, :] *= 1.0 + 3.0e-3 * rng.uniform(-1.0, 1.0, pe[:, 1:, :].shape)
+    peln = noise(nx, km + 1, ny)
+    peln[:, 0, :] = peln_c[:, :, 0]
+    pk = noise(nx, ny, km + 1)
+    pk[:, :, 0] = np.exp(KAPPA * peln_c[:, :, 0])
+    st = dict(
+        delp=halo(dpc), pt=halo(T), q=halo(q), qdiag=halo(qdiag), ua=halo(10.0 * rng.standard_normal((nx, ny, km))),
+        va=halo(10.0 * rng.standard_normal((nx, ny, km))), w=halo(0.5 * rng.standard_normal((nx, ny, km))),
+        u=np.asfortranarray(10.0 * rng.standard_normal(bd.shape("U", km))), v=np.asfortranarray(10.0 * rng.standard_normal(bd.shape("V", km))),
+        u_dt=np.asfortranarray(1.0e-3 * rng.standard_normal(bd.shape("A", km))), v_dt=np.asfortranarray(1.0e-3 * rng.standard_normal(bd.shape("A", km))),
+        t_dt=np.asfortranarray(t_dt), q_dt=np.asfortranarray(q_dt), delz=np.asfortranarray(delz),
+        ps=np.asfortranarray(rng.uniform(1.0, 2.0, bd.shape("A"))), pe=pe, peln=peln, pk=pk, pkz=noise(nx, ny, km), u_srf=noise(nx, ny), v_srf=noise(nx, ny))
+    if zero_tendencies:
+        for n in ("t_dt", "q_dt", "u_dt", "v_dt"):
+            st[n][...] = 0.0
+    return bd, st
+
+
+def checksum(st):
+    h = hashlib.sha256()
+    for n in sorted(st):
+        h.update(n.encode())
+        h.update(np.ascontiguousarray(st[n]).tobytes())
+    return h.hexdigest()
+
+
+# ---- the recorded cases: 6 x 4 columns (an interior of 4 x 2 inside the one ring update_dwinds_phys reads), 8 levels, nq = 8 of
+# ncnst = 9 tracers (qdiag holds the ninth), cld_amt = 7, w_diff = 8 (counts when nonhydrostatic).  name -> parameters; group = the
+# golden file the case is kept in (tests/golden/update_phys_<group>.npz)
+NX, NY, KM, NQ, NCNST = 6, 4, 8, 8, 9
+PTOP = 0.2      # = ak(1) of eta_levels(8)
+
+
+def _case(group, hyd, nwat, phys_hyd=True, has_qdt=True, tau_h2o=0.0, adjust_off=(), seed=0):
+    return dict(group=group, hydrostatic=hyd, phys_hydrostatic=phys_hyd, nwat=nwat, has_qdt=has_qdt, tau_h2o=tau_h2o, adjust_off=tuple(adjust_off),
+                cld_amt=7, w_diff=8, nq=NQ, ncnst=NCNST, km=KM, seed=seed, dt=DT, ptop=PTOP, gfs_phys=False)
+
+
+CASES = {}
+for _n in range(7):
+    CASES[f"hydro/nwat{_n}"] = _case("hydro_a" if _n < 4 else "hydro_b", True, _n, seed=40 + _n)
+for _n in (0, 2, 6):
+    CASES[f"nh_ph/nwat{_n}"] = _case("nh_ph", False, _n, phys_hyd=True, seed=50 + _n)
+    CASES[f"nh/nwat{_n}"] = _case("nh", False, _n, phys_hyd=False, seed=60 + _n)
+CASES["hydro/no_q_dt"] = _case("hydro_b", True, 6, has_qdt=False, seed=71)
+CASES["nh/no_q_dt"] = _case("nh", False, 6, phys_hyd=False, has_qdt=False, seed=72)
+CASES["hydro/tau_h2o_neg"] = _case("misc", True, 3, tau_h2o=-0.5, seed=73)
+CASES["nh/tau_h2o_pos"] = _case("misc", False, 6, phys_hyd=False, tau_h2o=2.0, seed=74)
+CASES["hydro/adjust_off"] = _case("misc", True, 6, adjust_off=(2, 8, 9), seed=75)
+CASES["nh_ph/adjust_off"] = _case("nh_ph", False, 3, adjust_off=(1, 9), seed=76)
+
+
+def species_of(c):
+    return dict(SPECIES_OF[c["nwat"]], cld_amt=c.get("cld_amt", 0), w_diff=c.get("w_diff", 0))
+
+
+def adjust_mass_of(c):
+    a = np.ones(c["ncnst"], dtype=np.int32)
+    for m in c.get("adjust_off", ()):
+        a[m - 1] = 0
+    return a
+
+
+def case_inputs(name):
+    c = CASES[name]
+    bd, st = state(NX, NY, c["km"], c["nq"], c["ncnst"], c["nwat"], c["seed"], ptop=c["ptop"])
+    return bd, st
