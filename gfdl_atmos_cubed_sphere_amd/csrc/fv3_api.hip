@@ -30,6 +30,7 @@
 #include "neg_adj.h"
 #include "subgrid_z.h"
 #include "phys_update.h"
+#include "held_suarez.h"
 #include "diag_kernels.h"
 #include "remap_kernels.h"
 #include "remap_fast.h"
@@ -163,6 +164,8 @@ struct fv3_ctx {
   // fv_update_phys (phys_update.h): qstar(k), p_fac(k) of the tau_h2o relaxation, 2 x npz on the device, and what was uploaded last
   double *up_tab = nullptr;
   std::vector<double> up_tab_host;
+  // Held_Suarez_Tend (held_suarez.h): the five latitude planes on the compute domain (fv3_grid_upload_lat)
+  double *hs_lat = nullptr;
   std::vector<double> host_area;   // prt_maxmin: area on the host, and g_sum's global_area
   double global_area = 0.;
   int march_tj_fused = kMarchTj;   // rows per segment of the fused d_sw kernels, transports and momentum (FV3_MI355X_MARCH_TJ_FUSED)
@@ -707,6 +710,7 @@ extern "C" int fv3_destroy(fv3_ctx *c) {
   work_free(c, &c->sg_wk);
   if (c->dw_dev) rt_free(c->dw_dev);
   if (c->up_tab) rt_free(c->up_tab);
+  if (c->hs_lat) rt_free(c->hs_lat);
   if (c->stream2) rt_stream_destroy(c->stream2);
   if (c->ev_fork) rt_event_destroy(c->ev_fork);
   if (c->ev_join) rt_event_destroy(c->ev_join);
@@ -4689,6 +4693,100 @@ extern "C" int fv3_fv_update_phys(fv3_ctx *c, const fv3_update_phys_params *p, c
   else if (tb == 1) RT(by_nwat(std::integral_constant<int, 1>{}));
   else if (tb == 2) RT(go(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}));
   else RT(by_nwat(std::integral_constant<int, 3>{}));
+  return 0;
+}
+
+// ---- Held_Suarez_Tend and age_of_air (held_suarez.h) ------------------------------------------------------------------------------
+extern "C" int fv3_grid_upload_lat(fv3_ctx *c, const double *lat) {
+  if (!c || !lat) return fail("fv3_grid_upload_lat: null argument");
+  if (!c->grid_ready) return fail("fv3_grid_upload_lat: context has no grid");
+  const Grid &g = c->g;
+  const size_t nc = g.nCC();
+  // hswf.F90:101-105, :130, :152, :180-184: each plane in the reference's own expression, with the host's libm
+  const double ty = 60.0, tz = 10.0, akap = 2. / 7., p0 = 100000.;
+  const double ap0k = 1. / std::pow(p0, akap);
+  std::vector<double> tab(5 * nc);
+  for (size_t n = 0; n < nc; n++) {
+    const double a = lat[n];
+    tab[n] = a;
+    tab[nc + n] = std::cos(a);
+    tab[2 * nc + n] = ty * std::sin(a) * std::sin(a);
+    tab[3 * nc + n] = tz * (ap0k / akap) * std::cos(a) * std::cos(a);
+    tab[4 * nc + n] = std::pow(std::cos(a), 4.0);
+  }
+  if (c->hs_lat) {   // a launch that an fv3_group still holds reads the old table: the queues run before it changes
+    if (int rc = grp_flush_all()) return rc;
+    RT(rtf_sync(c->stream));
+  } else {
+    RT(rt_malloc((void **)&c->hs_lat, tab.size() * sizeof(double)));
+  }
+  RT(rtf_h2d(c->hs_lat, tab.data(), tab.size() * sizeof(double), c->stream));
+  RT(rtf_sync(c->stream));
+  return 0;
+}
+
+extern "C" int fv3_held_suarez_tend(fv3_ctx *c, const fv3_held_suarez_params *p, const double *delp, const double *peln, const double *pe,
+                                    const double *pkz, const double *pt, const double *ua, const double *va, double *u_dt, double *v_dt,
+                                    double *t_dt) {
+  FV3_ENTRY(c);
+  if (!c || !c->grid_ready) return fail("fv3_held_suarez_tend: context has no grid");
+  if (!p || !delp || !peln || !pe || !pt || !ua || !va || !u_dt || !v_dt || !t_dt) return fail("fv3_held_suarez_tend: null parameters / field");
+  if (!p->zurita && !pkz) return fail("fv3_held_suarez_tend: null pkz (the standard troposphere branch reads it)");
+  const Grid &g = c->g;
+  if (g.npz < 1) return fail("fv3_held_suarez_tend: npz = %d < 1", g.npz);
+  if (!(p->pdt > 0.)) return fail("fv3_held_suarez_tend: pdt = %g <= 0", p->pdt);
+  if (p->zurita && !(p->rd_zur > 0.)) return fail("fv3_held_suarez_tend: zurita with rd_zur = %g <= 0", p->rd_zur);
+  if (p->zurita && !(p->pi > 0.)) return fail("fv3_held_suarez_tend: zurita with pi = %g <= 0", p->pi);
+  if (!(p->radius > 0.)) return fail("fv3_held_suarez_tend: radius = %g <= 0", p->radius);
+  if (!c->hs_lat) return fail("fv3_held_suarez_tend: no latitude table (fv3_grid_upload_lat)");
+  // hswf.F90:101-133, in its order
+  const double akap = 2. / 7.;
+  const double p0 = 100000.;
+  const double sday = 24. * 3600.;
+  const double pdt = p->pdt;
+  const double rdt = 1. / pdt;
+  const double rad_ratio = p->radius / 6371.0e3;
+  const double kf_day = sday * rad_ratio;
+  const double rkv = pdt / kf_day;
+  const double rka = pdt / (40. * kf_day);
+  const double rks = pdt / (4.0 * kf_day);
+  const double t_ms = 10. * rad_ratio;
+  const double t_st = 40. * rad_ratio;
+  const double tau = (t_st - t_ms) / std::log(100.);
+  const double rms = pdt / (t_ms * sday);
+  const double rmr = 1. / (1. + rms);
+  const double sigb = 0.7;
+  const double rsgb = 1. / (1. - sigb);
+  const double ap0k = 1. / std::pow(p0, akap);
+  const double algpk = std::log(ap0k);
+  const double rd_zur_rad = p->rd_zur * p->pi / 180.;
+  auto go = [&](auto S, auto Z) -> int {
+    HeldSuarezTend<decltype(S)::value, decltype(Z)::value> kf{g, p->fresh ? 1 : 0, pdt, sday, rdt, rkv, rka, rks - rka, rms, rmr, tau, t_ms, rsgb,
+                                                               ap0k, algpk, rd_zur_rad, c->hs_lat, delp, peln, pe, pkz, pt, ua, va, u_dt, v_dt, t_dt};
+    static_assert(decltype(kf)::CH == 256, "col_grid");
+    return launch_p(c, "held_suarez_tend", col_grid(g.nx * g.ny), 0, kf);
+  };
+  if (p->strat) {
+    if (p->zurita) RT(go(std::true_type{}, std::true_type{}));
+    else RT(go(std::true_type{}, std::false_type{}));
+  } else {
+    if (p->zurita) RT(go(std::false_type{}, std::true_type{}));
+    else RT(go(std::false_type{}, std::false_type{}));
+  }
+  return 0;
+}
+
+extern "C" int fv3_age_of_air(fv3_ctx *c, int km, double time, const double *pe, double *q) {
+  FV3_ENTRY(c);
+  if (!c || !c->grid_ready) return fail("fv3_age_of_air: context has no grid");
+  if (!pe || !q) return fail("fv3_age_of_air: null field");
+  if (km < 1) return fail("fv3_age_of_air: km = %d < 1", km);
+  if (!(time == time)) return fail("fv3_age_of_air: time is not a number");
+  const Grid &g = c->g;
+  const double tiny = 1.e-6, ascale = 5.e-6 / 60.;   // hswf.F90:228-230
+  AgeOfAir kf{g, km, time < tiny ? 1 : 0, ascale * time, pe, q};
+  static_assert(AgeOfAir::CH == 256, "col_grid");
+  RT(launch_p(c, "age_of_air", col_grid(g.nx * g.ny), 0, kf));
   return 0;
 }
 

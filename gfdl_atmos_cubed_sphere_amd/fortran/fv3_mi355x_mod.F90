@@ -28,6 +28,7 @@ module fv3_mi355x_mod
   public :: fv3_fv_subgrid_z, fv3_sg_params, fv3_grid_dwinds, fv3_grid_upload_dwinds, fv3_update_dwinds_phys
   public :: fv3_interpolate_vertical
   public :: fv3_fv_update_phys, fv3_update_phys_params
+  public :: fv3_grid_upload_lat, fv3_held_suarez_tend, fv3_held_suarez_params, fv3_age_of_air
 
   type, bind(C) :: fv3_domain
     integer(c_int) :: is, ie, js, je, ng, npx, npy, npz, grid_type
@@ -108,6 +109,14 @@ module fv3_mi355x_mod
     real(c_double) :: dt, ptop, tau_h2o = 0.0_c_double
     type(c_ptr) :: ak = c_null_ptr, bk = c_null_ptr   ! host addresses, npz + 1 each; read only when tau_h2o /= 0
     real(c_double) :: rdgas, rvgas, grav, cp_air, cp_vapor, kappa, c_liq, c_ice
+  end type
+
+  type, bind(C) :: fv3_held_suarez_params   ! Held_Suarez_Tend (driver/solo/hswf.F90:41): pdt, do_strat_HS_forcing, do_zurita_HS, rd_zur
+    real(c_double) :: pdt                   ! [deg], fresh /= 0: t_dt, u_dt, v_dt are taken as zero, not read, and written everywhere;
+    integer(c_int) :: strat = 1, zurita = 0 ! radius: fv_arrays_mod's (scaled for a small earth), pi: constants_mod's
+    real(c_double) :: rd_zur = 0.04_c_double
+    integer(c_int) :: fresh = 0
+    real(c_double) :: radius, pi
   end type
 
   type, bind(C) :: fv3_grid_dwinds    ! what update_dwinds_phys reads of the gridstruct on the sphere (fv_grid_utils.F90:3314-3326):
@@ -698,6 +707,26 @@ module fv3_mi355x_mod
       import :: c_int, c_ptr, fv3_update_phys_params
       type(c_ptr), value :: ctx, u_dt, v_dt, t_dt, q_dt, delp, pt, q, qdiag, ua, va, w, delz, ps, pe, peln, pk, pkz, u_srf, v_srf
       type(fv3_update_phys_params), intent(in) :: p
+    end function
+    ! what Held_Suarez_Tend reads of the gridstruct: lat = agrid(is:ie, js:je, 2), HOST, contiguous; once per context
+    integer(c_int) function fv3_grid_upload_lat(ctx, lat) bind(C, name="fv3_grid_upload_lat")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, lat
+    end function
+    ! Held_Suarez_Tend (driver/solo/hswf.F90:41-207; the do_Held_Suarez branch of driver/solo/fv_phys.F90:620-627): the forcing added to
+    ! t_dt (is:ie, js:je, npz) and, where the bottom friction acts, to u_dt, v_dt (A x npz).  pkz may be c_null_ptr with zurita.  The
+    ! caller goes on with fv3_fv_update_phys and what follows it
+    integer(c_int) function fv3_held_suarez_tend(ctx, p, delp, peln, pe, pkz, pt, ua, va, u_dt, v_dt, t_dt) bind(C, name="fv3_held_suarez_tend")
+      import :: c_int, c_ptr, fv3_held_suarez_params
+      type(c_ptr), value :: ctx, delp, peln, pe, pkz, pt, ua, va, u_dt, v_dt, t_dt
+      type(fv3_held_suarez_params), intent(in) :: p
+    end function
+    ! age_of_air (driver/solo/hswf.F90:209-245): q = c_loc(q(isd, jsd, 1, iq)), one tracer; time: the accumulated time [s]
+    integer(c_int) function fv3_age_of_air(ctx, km, time, pe, q) bind(C, name="fv3_age_of_air")
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: ctx, pe, q
+      integer(c_int), value :: km
+      real(c_double), value :: time
     end function
     ! interpolate_vertical (tools/fv_diagnostics.F90:4910-4948): a3 (km layers) at the pressure plev [Pa] into a2 (is:ie, js:je).
     ! in_ng = 0: a3 on the compute domain, as the reference's argument; in_ng = ng: a state field with its halo, in the place of the

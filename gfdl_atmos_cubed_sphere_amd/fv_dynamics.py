@@ -234,6 +234,40 @@ class FvDynamics:
         if gfs_phys:                                                       # :738-742
             self.cubed_to_latlon()
 
+    # -- Held-Suarez forcing --------------------------------------------------------------------------------------
+    def held_suarez(self, dt: float, strat: bool = True, zurita: bool = False, rd_zur: float = 1.0 / 25.0, age_tracer: int = 0,
+                    time_total: float = 0.0):
+        """the do_Held_Suarez path of fv_phys (driver/solo/fv_phys.F90:292-313, :620-627, :675-687) on the resident state, a tile or
+        the six faces alike: Held_Suarez_Tend with fresh set writes d["t_dt"], d["u_dt"], d["v_dt"] (the reference zeroes them
+        first), fv_update_phys applies them (moist_phys false, no nudging; the reference's q_dt is zero there, which leaves the
+        tracers and the air mass with their bits, so none is passed), and age_of_air sets the tracer age_tracer (1-based, 0 = none;
+        the reference's -DDO_AGE build takes the last one) from time_total.  No field leaves the device."""
+        d, ctx = self.dc.d, self.ctx
+        npz = ctx.npz
+        if not 0 <= age_tracer <= self.nq:
+            raise ValueError(f"FvDynamics.held_suarez: age_tracer = {age_tracer} is not a tracer of 1..{self.nq} (0 = none)")
+        if "t_dt" not in d:
+            d["t_dt"] = ctx.empty("CC", npz)
+        for n in ("u_dt", "v_dt"):
+            if n not in d:
+                d[n] = ctx.zeros("A", npz)                                 # (the halo: fv_update_phys' exchange fills it)
+        ctx.held_suarez_tend(dt, d["delp"], d["peln"], d["pe"], d["pkz"], d["pt"], d["ua"], d["va"], d["u_dt"], d["v_dt"], d["t_dt"],
+                             strat=strat, zurita=zurita, rd_zur=rd_zur, fresh=True, radius=self.radius)
+        self.fv_update_phys(dt, d["t_dt"], None, d["u_dt"], d["v_dt"])
+        if age_tracer:                                                     # hswf.F90:202-205
+            q = d["q"]
+            if hasattr(q, "a"):                                            # six faces: one tracer view per face
+                for t, c in enumerate(ctx.ctxs):
+                    c.age_of_air(npz, time_total, d["pe"][t], _TracerView(q[t], age_tracer - 1))
+            else:
+                ctx.age_of_air(npz, time_total, d["pe"], _TracerView(q, age_tracer - 1))
+
+    def forced_step(self, bdt: float, **hs):
+        """atmosphere_step followed by held_suarez: one step of a Held-Suarez climate (the solo driver's atmosphere_dynamics and
+        fv_phys with do_Held_Suarez).  A hydrostatic run starts with d["pkz"] set as p_var sets it: step_from_temperature divides by it."""
+        self.atmosphere_step(bdt)
+        self.held_suarez(bdt, **hs)
+
     # -- neg_adj3 -------------------------------------------------------------------------------------------------
     def _prt_negative(self, when: str):
         """prt_negative (fv_sg.F90:1372-1392) of T and the six species: the global minimum, reported when below its threshold"""

@@ -87,6 +87,9 @@ def doubly_periodic(bd: Bounds, npx: int, npy: int, dx_const: float = 1000.0, dy
     m["fC"][...] = f
     m["sin_sg"] = np.ones(bd.shape("A", 9), order="F")
     m["cos_sg"] = np.zeros(bd.shape("A", 9), order="F")
+    # agrid of the Cartesian grid (fv_grid_tools.F90, grid_type 4): longitude 0, the one latitude deglat -- what Held_Suarez_Tend reads
+    m["agrid"] = np.zeros(bd.shape("A") + (2,), order="F")
+    m["agrid"][..., 1] = np.deg2rad(deglat)
     g.da_min = g.da_min_c = dx_const * dy_const
     return g
 

@@ -37,7 +37,8 @@ EXPORTS = ["fv3_last_error", "fv3_create", "fv3_destroy", "fv3_set_stream", "fv3
            "fv3_set_dp_ref", "fv3_update_dz_c", "fv3_set_condensate", "fv3_set_fast_tau_w", "fv3_set_ray_fast", "fv3_ray_fast", "fv3_mix_dp", "fv3_compute_aam", "fv3_consv_am_apply", "fv3_riem_solver_c", "fv3_update_dz_d", "fv3_riem_solver3",
            "fv3_p_grad_c", "fv3_nh_p_grad", "fv3_split_p_grad", "fv3_grad1_p_update", "fv3_d_sw_inline_q", "fv3_flux_accum", "fv3_fill2d_mass", "fv3_fill2d_apply", "fv3_set_remap_te", "fv3_profile_report_timers", "fv3_prt_maxmin", "fv3_pk3_halo", "fv3_pe_halo", "fv3_geopk", "fv3_zh_from_delz", "fv3_set_ak_bk", "fv3_set_moist", "fv3_lagrangian_to_eulerian",
            "fv3_tracer_2d_prep", "fv3_tracer_2d_scale", "fv3_tracer_2d_step", "fv3_neg_adj3",
-           "fv3_fv_subgrid_z", "fv3_grid_upload_dwinds", "fv3_update_dwinds_phys", "fv3_interpolate_vertical", "fv3_fv_update_phys"]
+           "fv3_fv_subgrid_z", "fv3_grid_upload_dwinds", "fv3_update_dwinds_phys", "fv3_interpolate_vertical", "fv3_fv_update_phys",
+           "fv3_grid_upload_lat", "fv3_held_suarez_tend", "fv3_age_of_air"]
 
 
 class Fv3Error(RuntimeError):
@@ -162,6 +163,11 @@ class _UpdatePhysParams(C.Structure):
                                        "ice_wat", "snowwat", "graupel", "cld_amt", "w_diff"]] + [("adjust_mass", _ip)] + [
         (n, C.c_double) for n in ["dt", "ptop", "tau_h2o"]] + [("ak", _dp), ("bk", _dp)] + [
         (n, C.c_double) for n in ["rdgas", "rvgas", "grav", "cp_air", "cp_vapor", "kappa", "c_liq", "c_ice"]]
+
+
+class _HeldSuarezParams(C.Structure):
+    _fields_ = [("pdt", C.c_double), ("strat", C.c_int), ("zurita", C.c_int), ("rd_zur", C.c_double), ("fresh", C.c_int),
+                ("radius", C.c_double), ("pi", C.c_double)]
 
 
 SG_SPECIES = ("sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel")
@@ -518,6 +524,37 @@ class Context:
         self.lib.check(self.lib.dll.fv3_fv_update_phys(self.h, C.byref(pr), _pp(u_dt), _pp(v_dt), _pp(t_dt), _pp(q_dt), _pp(delp), _pp(pt),
                                                        _pp(q), _pp(qdiag), _pp(ua), _pp(va), _pp(w), _pp(delz), _pp(ps), _pp(pe), _pp(peln),
                                                        _pp(pk), _pp(pkz), _pp(u_srf), _pp(v_srf)), "fv3_fv_update_phys")
+
+    def upload_lat(self, lat=None):
+        """fv3_grid_upload_lat: the latitude of the cell centres on the compute domain, agrid(is:ie, js:je, 2) -- what Held_Suarez_Tend
+        reads of the gridstruct.  Default: the gridstruct's agrid (A x 2, as cubed_sphere.py forms it).  Once per context."""
+        if lat is None:
+            if "agrid" not in self.grid.m:
+                raise Fv3Error("upload_lat: the gridstruct has no agrid")
+            b = self.bd
+            lat = b.view(np.asarray(self.grid.m["agrid"])[..., 1], "A", b.is_, b.ie, b.js, b.je)
+        lat = np.asfortranarray(lat, dtype=np.float64)
+        if lat.shape != (self.bd.nx, self.bd.ny):
+            raise Fv3Error(f"upload_lat: lat has the shape {lat.shape}, the compute domain {(self.bd.nx, self.bd.ny)}")
+        self.lib.check(self.lib.dll.fv3_grid_upload_lat(self.h, lat.ctypes.data_as(_dp)), "fv3_grid_upload_lat")
+        self.lat_ready = True
+
+    def held_suarez_tend(self, pdt, delp, peln, pe, pkz, pt, ua, va, u_dt, v_dt, t_dt, strat=True, zurita=False, rd_zur=1.0 / 25.0,
+                         fresh=False, radius=6.3712e6, pi=3.14159265358979323846):
+        """Held_Suarez_Tend (driver/solo/hswf.F90:41-207): the Held-Suarez forcing added to t_dt (is:ie, js:je, npz; no halo) and, where
+        the bottom friction acts, to u_dt, v_dt (A x npz).  fresh: the incoming tendencies are taken as zero, not read, and every cell
+        of the three on the compute domain is written.  radius: fv_arrays_mod's (scaled for a small earth); pi: constants_mod's.  The
+        latitude table is uploaded from the gridstruct on first use."""
+        if not getattr(self, "lat_ready", False):
+            self.upload_lat()
+        pr = _HeldSuarezParams(float(pdt), int(bool(strat)), int(bool(zurita)), float(rd_zur), int(bool(fresh)), float(radius), float(pi))
+        self.lib.check(self.lib.dll.fv3_held_suarez_tend(self.h, C.byref(pr), _pp(delp), _pp(peln), _pp(pe), _pp(pkz), _pp(pt), _pp(ua), _pp(va),
+                                                         _pp(u_dt), _pp(v_dt), _pp(t_dt)), "fv3_held_suarez_tend")
+
+    def age_of_air(self, km, time, pe, q):
+        """age_of_air (driver/solo/hswf.F90:209-245): the age tracer q (ONE tracer, A x km) zeroed when time < 1e-6, else set to
+        5e-6 / 60 * time where pe(i, k, j) >= 75000 Pa"""
+        self.lib.check(self.lib.dll.fv3_age_of_air(self.h, C.c_int(int(km)), C.c_double(float(time)), _pp(pe), _pp(q)), "fv3_age_of_air")
 
     def interpolate_vertical(self, km, plev, peln, a3, a2, in_ng=0):
         """interpolate_vertical (tools/fv_diagnostics.F90:4910-4948): a2 (is:ie, js:je) = a3 (km layers) at the pressure plev [Pa], linear

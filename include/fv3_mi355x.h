@@ -744,6 +744,54 @@ int fv3_fv_update_phys(fv3_ctx *ctx, const fv3_update_phys_params *p, const doub
                        double *delp, double *pt, double *q, double *qdiag, double *ua, double *va, const double *w, double *delz,
                        double *ps, double *pe, double *peln, double *pk, double *pkz, double *u_srf, double *v_srf);
 
+/* fv3_grid_upload_lat -- what Held_Suarez_Tend reads of the gridstruct, agrid(is:ie, js:je, 2) (driver/solo/hswf.F90:72, :152, :163,
+ * :171, :180-184): lat is the latitude [rad] of the cell centres on the compute domain, (is:ie, js:je), HOST.  Once per context, before
+ * the first fv3_held_suarez_tend.  The host forms five planes with its libm, each in the reference's own expression, and uploads
+ * them: agrid; COS(agrid); ty*SIN(agrid)*SIN(agrid); tz*(ap0k/akap)*COS(agrid)*COS(agrid); COS(agrid)**4.0 -- no sin, cos or pow runs
+ * on the device.  Written: the context's table, nothing else.  Refused: null arguments, a context without a grid.  A second call
+ * replaces the table (queued launches of an fv3_group run first). */
+int fv3_grid_upload_lat(fv3_ctx *ctx, const double *lat);
+
+/* fv3_held_suarez_tend -- Held_Suarez_Tend, driver/solo/hswf.F90:41-207, the forcing of the solo driver's do_Held_Suarez branch
+ * (driver/solo/fv_phys.F90:620-627), whose tendencies go to fv_update_phys (:675-687; fv3_fv_update_phys).  One launch (six faces of
+ * an fv3_group: one), one thread per column, one walk up the column (k = npz .. 1, :147).  pl(k) = delp / (peln(k+1) - peln(k));
+ * with strat and pl <= 1e2 the mesosphere branch (:149-154), with strat and 1e2 < pl <= 100e2 the stratosphere branch (:156-165),
+ * both continuing teq upwards from the level below; else the troposphere (:167-186) in the standard form (reads pkz) or, with zurita,
+ * the form of :171-178 (rd_zur in degrees), followed by the bottom friction (:187-196) where sigl > sigb = 0.7.  The scalars of
+ * :101-133 are formed on the host in the reference's order from pdt, radius (fv_arrays_mod's, scaled for a small earth) and pi
+ * (constants_mod's; read only with zurita).  log and exp are include/fv3_math.h where the reference calls its libm.
+ * fresh /= 0: the incoming t_dt, u_dt, v_dt are taken as zero and not read, and every cell of the three on the compute domain is
+ * written -- bit-identical, the sign of zero included, with zeroing them and calling with fresh = 0 (the memsets of
+ * fv_phys.F90:292-313).
+ * delp, pt, ua, va, u_dt, v_dt: A x npz; t_dt, pkz (is:ie, js:je, npz): NO halo; pe (is-1:ie+1, npz+1, js-1:je+1); peln (is:ie,
+ * npz+1, js:je).  Device pointers.  pkz may be NULL with zurita.
+ * Written, on the compute domain only: t_dt; u_dt, v_dt where the friction acts (with fresh: everywhere).  Nothing else: halos and
+ * every input keep their bits.  The reference's unused arguments are not part of the call: u, v, q, q_dt, delz, phis, hydrostatic,
+ * ak, bk, ks, master, Time; time_total is fv3_age_of_air's.
+ * Refused (status 1 and a message, nothing launched): null fields; npz < 1; pdt <= 0; radius <= 0; zurita with rd_zur <= 0 or
+ * pi <= 0; no latitude table uploaded.
+ * Not defined, because the reference is not: a column whose bottom layer already has pl <= 100e2 with strat -- the reference reads
+ * pl(npz+1) and teq(npz+1) there.
+ * Not built: the rest of fv_phys.F90 (do_surf_drag, Reed physics, the mixed layer, the gray radiation, the terminator chemistry, the
+ * clock tracers), send_data, the regional / nested paths. */
+typedef struct fv3_held_suarez_params {
+  double pdt;            /* the physics step [s] */
+  int strat, zurita;     /* do_strat_HS_forcing, do_zurita_HS */
+  double rd_zur;         /* [deg], read only with zurita */
+  int fresh;             /* /= 0: t_dt, u_dt, v_dt are taken as zero, not read, and written everywhere */
+  double radius, pi;     /* fv_arrays_mod's radius, constants_mod's pi */
+} fv3_held_suarez_params;
+int fv3_held_suarez_tend(fv3_ctx *ctx, const fv3_held_suarez_params *p, const double *delp, const double *peln, const double *pe,
+                         const double *pkz, const double *pt, const double *ua, const double *va, double *u_dt, double *v_dt, double *t_dt);
+
+/* fv3_age_of_air -- age_of_air, driver/solo/hswf.F90:209-245, which the reference calls under -DDO_AGE from inside Held_Suarez_Tend
+ * with the last tracer (:202-205): q, ONE tracer in the A layout x km, is zeroed when time < 1e-6, otherwise set to ascale * time
+ * (ascale = 5e-6 / 60) where pe(i, k, j) >= 75000 Pa and left alone where not.  time: the accumulated time since the start [s].
+ * pe (is-1:ie+1, km+1, js-1:je+1), read on levels 1..km of the compute domain.  Device pointers.  One launch (six faces of an
+ * fv3_group: one).  Written: q on the compute domain, the cells named above; the halo keeps its bits.  Refused: null fields,
+ * km < 1, time not a number. */
+int fv3_age_of_air(fv3_ctx *ctx, int km, double time, const double *pe, double *q);
+
 /* fv3_interpolate_vertical -- interpolate_vertical, tools/fv_diagnostics.F90:4910-4948 (call sites :2017 the 850 hPa vorticity, :2198 and :2263-2299
  * the relative humidity at 200 hPa and at ten CMIP levels, :2971-2979 condensate at 200 / 500 / 850 hPa, :3522): the field a3 (km layers) at the one pressure plev [Pa], linear in the layer-mean log pressure
  * pm(k) = 0.5 (peln(k) + peln(k+1)) (:4930); at or above pm(1) it is a3(1), at or below pm(km) it is a3(km) (:4933-4936).

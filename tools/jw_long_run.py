@@ -1,7 +1,11 @@
 """BASELINE config 2 run for real: the Jablonowski-Williamson baroclinic wave (test_case 13) on the C96 L79 hydrostatic cubed sphere,
 whole sphere on one MI355X, `--days` days of dt_atmos = 1800 s (k_split 2 x n_split 6).  Every 12 h:
 global air mass (must stay put), min / max surface pressure (JW06: the wave deepens to ~940-950 hPa around day 9), max |u|, max
-|v|.  Prints one JSON object."""
+|v|.  Prints one JSON object.
+--held-suarez: a Held-Suarez climate in the place of the adiabatic wave -- FvDynamics.forced_step (fv_dynamics, then Held_Suarez_Tend
+and fv_update_phys on the device, no field downloaded between steps) from the same initial state, with --zurita and --no-strat for
+the reference's do_zurita_HS and do_strat_HS_forcing; every 12 h also the maximum of the zonal-mean zonal wind (ua in 2-degree
+latitude bands, area-weighted, over bands and levels) and the global range of T."""
 from __future__ import annotations
 
 import argparse
@@ -28,6 +32,9 @@ def main():
     ap.add_argument("--prod", action="store_true", help="the damping set of a production namelist: nord 3, do_vort_damp, vtdm4 0.06, d_con 1, dddmp 0.5")
     ap.add_argument("--flags", type=str, default="", help="JSON of DynFlags overrides")
     ap.add_argument("--nh", action="store_true", help="nonhydrostatic (BASELINE config 3 at --nx 384 --npz 127 --dt-atmos 225 --n-split 5)")
+    ap.add_argument("--held-suarez", action="store_true", help="forced_step (Held-Suarez forcing on the device) in the place of the adiabatic step")
+    ap.add_argument("--zurita", action="store_true", help="with --held-suarez: the do_zurita_HS form of the equilibrium temperature")
+    ap.add_argument("--no-strat", action="store_true", help="with --held-suarez: do_strat_HS_forcing off")
     a = ap.parse_args()
     import torch
     from gfdl_atmos_cubed_sphere_amd import lib as L
@@ -57,7 +64,9 @@ def main():
             pkz = (pe[:, :, 1:] ** fl.akap - pe[:, :, :-1] ** fl.akap) / (fl.akap * (peln[:, :, 1:] - peln[:, :, :-1]))
         else:
             pkz = ((-fl.rdgas / fl.grav) * s_["delp"][c] * s_["pt"][c] / s_["delz"]) ** fl.akap
-        s_["pt"][c] = s_["pt"][c] / pkz
+        if not a.held_suarez:      # fv.step takes theta; forced_step takes T, as the drivers hold it
+            s_["pt"][c] = s_["pt"][c] / pkz
+        s_["pkz"] = np.asfortranarray(pkz)
     streams = [torch.cuda.Stream() for _ in range(6)]
     mctx = MultiContext([L.Context(g, npz, stream=fs.cuda_stream) for g, fs in zip(gs, streams)])
     nq = a.nq
@@ -74,8 +83,24 @@ def main():
     zero = np.zeros_like(st[0]["delp"])
     fv.dc.set_state([s_["u"] for s_ in st], [s_["v"] for s_ in st], [s_.get("w", zero) for s_ in st], [s_["delp"] for s_ in st],
                     [s_["pt"] for s_ in st], [s_.get("delz", bd.zeros("CC", npz)) for s_ in st], [s_["phis"] for s_ in st])
+    if a.held_suarez and hyd:      # p_var: the hydrostatic T -> theta_v conversion of fv_dynamics divides by the resident pkz
+        fv.dc.d["pkz"].upload([s_["pkz"] for s_ in st])
     del st
     areas = [np.asarray(g.m["area"])[c] for g in gs]
+    hs = dict(strat=not a.no_strat, zurita=a.zurita)
+    step = (lambda: fv.forced_step(a.dt_atmos, **hs)) if a.held_suarez else (lambda: fv.step(a.dt_atmos))
+    band = [np.clip(((np.asarray(g.m["agrid"])[..., 1][c] + 0.5 * np.pi) / np.deg2rad(2.0)).astype(int), 0, 89) for g in gs]
+    band_area = np.bincount(np.concatenate([b_.ravel() for b_ in band]), np.concatenate([ar.ravel() for ar in areas]), 90)
+
+    def hs_diag():
+        d = fv.dc.d
+        ua, pt = d["ua"].download(), d["pt"].download()
+        ubar = np.zeros((90, npz))
+        for k in range(npz):
+            ubar[:, k] = np.bincount(np.concatenate([b_.ravel() for b_ in band]),
+                                     np.concatenate([(x[c][:, :, k] * ar).ravel() for x, ar in zip(ua, areas)]), 90)
+        ubar /= np.maximum(band_area, 1.0e-30)[:, None]
+        return {"ubar_max": float(ubar.max()), "T_min": float(min(x[c].min() for x in pt)), "T_max": float(max(x[c].max() for x in pt))}
 
     def diag(day):
         d = fv.dc.d
@@ -87,19 +112,21 @@ def main():
             q = d["q"].download()
             tm = [float(sum(np.sum(q_[c][..., iq] * x[c] * ar[:, :, None]) for q_, x, ar in zip(q, dp, areas))) for iq in range(nq)]
             tr = {"tracer_mass": tm, "q_min": float(min(q_[c].min() for q_ in q)), "q_max": float(max(q_[c].max() for q_ in q))}
+        if a.held_suarez and day > 0.0:
+            tr = dict(tr, **hs_diag())
         return {**tr, "day": day, "mass": mass, "ps_min_hPa": float(min(p_.min() for p_ in ps)) / 100.0,
                 "ps_max_hPa": float(max(p_.max() for p_ in ps)) / 100.0,
                 "u_max": float(max(np.abs(bd.view(x, "U", bd.is_, bd.ie, bd.js, bd.je + 1)).max() for x in u)),
                 "v_max": float(max(np.abs(bd.view(x, "V", bd.is_, bd.ie + 1, bd.js, bd.je)).max() for x in v)),
                 "finite": bool(all(np.isfinite(x[c]).all() for x in dp))}
     out = [diag(0.0)]
-    fv.step(a.dt_atmos)
+    step()
     torch.cuda.synchronize()
     nsteps = int(round(a.days * 86400.0 / a.dt_atmos))
     every = int(round(43200.0 / a.dt_atmos))
     t0 = time.perf_counter()
     for n in range(2, nsteps + 1):
-        fv.step(a.dt_atmos)
+        step()
         if n % every == 0:
             torch.cuda.synchronize()
             out.append(diag(n * a.dt_atmos / 86400.0))
@@ -114,7 +141,8 @@ def main():
                       "sypd": a.days / 365.0 / (wall / 86400.0), "mass_drift_rel": abs(out[-1]["mass"] - m0) / m0,
                       "nq": nq, "tracer_mass_drift_rel_max": (max(abs(b_ - a_) / abs(a_) for a_, b_ in zip(out[0]["tracer_mass"], out[-1]["tracer_mass"]))
                                                               if nq else None),
-                      "ps_min_hPa_final": out[-1]["ps_min_hPa"], "build_id": L.build_id(), "series": out}))
+                      "ps_min_hPa_final": out[-1]["ps_min_hPa"],
+                      "held_suarez": dict(hs) if a.held_suarez else None, "build_id": L.build_id(), "series": out}))
     mctx.close()
 
 
