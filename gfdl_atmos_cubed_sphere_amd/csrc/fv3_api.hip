@@ -31,6 +31,7 @@
 #include "subgrid_z.h"
 #include "phys_update.h"
 #include "held_suarez.h"
+#include "reed_phys.h"
 #include "diag_kernels.h"
 #include "remap_kernels.h"
 #include "remap_fast.h"
@@ -166,6 +167,13 @@ struct fv3_ctx {
   std::vector<double> up_tab_host;
   // Held_Suarez_Tend (held_suarez.h): the five latitude planes on the compute domain (fv3_grid_upload_lat)
   double *hs_lat = nullptr;
+  // reed_sim_physics (reed_phys.h): Tsurf and the SST factor of qsats on the compute domain (fv3_grid_upload_reed) and the reed_test they
+  // were formed for; the six coefficient planes of the boundary-layer solve, 6 x (is:ie, js:je, npz), a work array under the poison
+  // contract; the terminator's k1 over the A layout (fv3_grid_upload_terminator)
+  double *reed_tab = nullptr;
+  int reed_tab_test = -1;
+  double *reed_wk = nullptr;
+  double *term_k1 = nullptr;
   std::vector<double> host_area;   // prt_maxmin: area on the host, and g_sum's global_area
   double global_area = 0.;
   int march_tj_fused = kMarchTj;   // rows per segment of the fused d_sw kernels, transports and momentum (FV3_MI355X_MARCH_TJ_FUSED)
@@ -711,6 +719,9 @@ extern "C" int fv3_destroy(fv3_ctx *c) {
   if (c->dw_dev) rt_free(c->dw_dev);
   if (c->up_tab) rt_free(c->up_tab);
   if (c->hs_lat) rt_free(c->hs_lat);
+  if (c->reed_tab) rt_free(c->reed_tab);
+  work_free(c, &c->reed_wk);
+  if (c->term_k1) rt_free(c->term_k1);
   if (c->stream2) rt_stream_destroy(c->stream2);
   if (c->ev_fork) rt_event_destroy(c->ev_fork);
   if (c->ev_join) rt_event_destroy(c->ev_join);
@@ -4787,6 +4798,180 @@ extern "C" int fv3_age_of_air(fv3_ctx *c, int km, double time, const double *pe,
   AgeOfAir kf{g, km, time < tiny ? 1 : 0, ascale * time, pe, q};
   static_assert(AgeOfAir::CH == 256, "col_grid");
   RT(launch_p(c, "age_of_air", col_grid(g.nx * g.ny), 0, kf));
+  return 0;
+}
+
+// ---- reed_sim_physics and DCMIP2016_terminator_advance (reed_phys.h) ---------------------------------------------------------------
+static const char *reed_consts_bad(const fv3_reed_consts *k) {
+  if (!(k->grav > 0.)) return "grav";
+  if (!(k->rdgas > 0.)) return "rdgas";
+  if (!(k->rvgas > 0.)) return "rvgas";
+  if (!(k->cp_air > 0.)) return "cp_air";
+  if (!(k->radius > 0.)) return "radius";
+  if (!(k->pi > 0.)) return "pi";
+  return nullptr;
+}
+
+extern "C" int fv3_grid_upload_reed(fv3_ctx *c, const double *lat, int reed_test, const fv3_reed_consts *k) {
+  if (!c || !lat || !k) return fail("fv3_grid_upload_reed: null argument");
+  if (!c->grid_ready) return fail("fv3_grid_upload_reed: context has no grid");
+  if (reed_test < 0 || reed_test > 2) return fail("fv3_grid_upload_reed: reed_test = %d is not 0, 1 or 2", reed_test);
+  if (const char *bad = reed_consts_bad(k)) return fail("fv3_grid_upload_reed: %s <= 0", bad);
+  const Grid &g = c->g;
+  const size_t nc = g.nCC();
+  // fv_phys.F90:74-85
+  const double tice = 273.16;
+  const double dc_vap = k->cp_vapor - k->c_liq;
+  const double Lv0 = k->hlv - dc_vap * tice;
+  // :2516-2551
+  const double rair = k->rdgas, a = k->radius, omega_r = k->omega, pi = k->pi;
+  const double rh2o = 461.5;
+  const double zvir = (rh2o / rair) - 1.;
+  const double SST_tc = 302.15, T00 = 288.0, u0 = 35.0;
+  const double latw = 2.0 * pi / 9.0, eta0 = 0.252;
+  const double etav = (1. - eta0) * 0.5 * pi;
+  const double q0 = 0.021;
+  std::vector<double> tab(2 * nc);
+  for (size_t n = 0; n < nc; n++) {
+    double Tsurf;
+    if (reed_test == 1) {   // :2573-2577, each power as the reference's compiler forms it: **0.5 and **1.5 through pow, the rest by products
+      const double sl = std::sin(lat[n]), cl = std::cos(lat[n]);
+      const double s2 = sl * sl, s3 = s2 * sl, s6 = s3 * s3, c2 = cl * cl, c3 = c2 * cl;   // x**6 = (x*x*x)**2
+      const double x = lat[n] / latw, x2 = x * x;
+      Tsurf = (T00 + pi * u0 / rair * 1.5 * std::sin(etav) * std::pow(std::cos(etav), 0.5) *
+                         ((-(2. * s6 * (c2 + 1. / 3.)) + 10. / 63.) * u0 * std::pow(std::cos(etav), 1.5) +
+                          (8. / 5. * c3 * (s2 + 2. / 3.) - pi / 4.) * a * omega_r * 0.5)) /
+              (1. + zvir * q0 * std::exp(-(x2 * x2)));
+    } else if (reed_test == 0) {
+      Tsurf = SST_tc;
+    } else {
+      Tsurf = 1.E25;
+    }
+    tab[n] = Tsurf;
+    tab[nc + n] = std::exp((dc_vap * std::log(Tsurf / tice) + Lv0 * (Tsurf - tice) / (Tsurf * tice)) / k->rvgas);   // :2719
+  }
+  if (c->reed_tab) {   // a launch that an fv3_group still holds reads the old table: the queues run before it changes
+    if (int rc = grp_flush_all()) return rc;
+    RT(rtf_sync(c->stream));
+  } else {
+    RT(rt_malloc((void **)&c->reed_tab, tab.size() * sizeof(double)));
+  }
+  RT(rtf_h2d(c->reed_tab, tab.data(), tab.size() * sizeof(double), c->stream));
+  RT(rtf_sync(c->stream));
+  c->reed_tab_test = reed_test;
+  return 0;
+}
+
+extern "C" int fv3_grid_download_reed(fv3_ctx *c, double *tab) {
+  if (!c || !tab) return fail("fv3_grid_download_reed: null argument");
+  if (!c->reed_tab) return fail("fv3_grid_download_reed: no Reed table (fv3_grid_upload_reed)");
+  RT(rtf_d2h(tab, c->reed_tab, 2 * c->g.nCC() * sizeof(double), c->stream));
+  RT(rtf_sync(c->stream));
+  return 0;
+}
+
+extern "C" int fv3_reed_sim_phys(fv3_ctx *c, const fv3_reed_params *p, const double *delp, const double *pt, const double *ua, const double *va,
+                                 const double *q, const double *pe, const double *peln, const double *phis, const double *delz, double *u_dt,
+                                 double *v_dt, double *t_dt, double *q_dt, double *rain) {
+  FV3_ENTRY(c);
+  if (!c || !c->grid_ready) return fail("fv3_reed_sim_phys: context has no grid");
+  if (!p || !delp || !pt || !ua || !va || !q || !pe || !peln || !phis || !u_dt || !v_dt || !t_dt || !q_dt || !rain)
+    return fail("fv3_reed_sim_phys: null parameters / field");
+  if (!p->hydrostatic && !delz) return fail("fv3_reed_sim_phys: null delz with hydrostatic = 0");
+  const Grid &g = c->g;
+  if (g.npz < 1) return fail("fv3_reed_sim_phys: npz = %d < 1", g.npz);
+  if (!(p->pdt > 0.)) return fail("fv3_reed_sim_phys: pdt = %g <= 0", p->pdt);
+  if (p->reed_test < 0 || p->reed_test > 2) return fail("fv3_reed_sim_phys: reed_test = %d is not 0, 1 or 2", p->reed_test);
+  if (const char *bad = reed_consts_bad(&p->k)) return fail("fv3_reed_sim_phys: %s <= 0", bad);
+  if (!c->reed_tab) return fail("fv3_reed_sim_phys: no Reed table (fv3_grid_upload_reed)");
+  if (c->reed_tab_test != p->reed_test)
+    return fail("fv3_reed_sim_phys: the Reed table was uploaded for reed_test = %d, the call has reed_test = %d", c->reed_tab_test, p->reed_test);
+  if (!c->reed_wk) RT(work_alloc(c, "reed_wk", 0, &c->reed_wk, 6 * g.nCC() * (size_t)g.npz));
+  // fv_phys.F90:74, :548-549, :2516-2545: each scalar a leading sub-expression of the reference's
+  const double e0 = 610.71, rh2o = 461.5, latvap = 2.5e6, T0 = 273.16, rhow = 1000.0;
+  ReedScalars s;
+  s.pdt = p->pdt;
+  s.rdt = 1. / p->pdt;
+  s.gravit = p->k.grav;
+  s.rair = p->k.rdgas;
+  s.cpair = p->k.cp_air;
+  s.kap = s.rair / s.cpair;
+  s.zvir = (rh2o / s.rair) - 1.;
+  const double epsilo = s.rair / rh2o;
+  s.ee0 = epsilo * e0;
+  s.elv = epsilo * latvap;
+  s.lvcp = latvap / s.cpair;
+  s.lvrv = latvap / rh2o;
+  s.rT0 = 1. / T0;
+  s.grw = s.gravit * rhow;
+  s.rog = s.rair / s.gravit;
+  s.c04sqC = 0.4 * std::sqrt(0.0011);
+  s.rgrav = 1. / p->k.grav;
+  s.rdrg = p->k.rdgas * s.rgrav;
+  s.zvir_w = p->k.rvgas / p->k.rdgas - 1.;
+  auto go = [&](auto Cn, auto A, auto H) -> int {
+    ReedSimPhys<decltype(Cn)::value, decltype(A)::value, decltype(H)::value> kf{g, p->fresh ? 1 : 0, p->reed_test, p->reed_cond_only ? 1 : 0, s,
+                                                                               c->reed_tab, delp, pt, ua, va, q, pe, peln, phis, delz, u_dt, v_dt,
+                                                                               t_dt, q_dt, rain, c->reed_wk};
+    static_assert(decltype(kf)::CH == 256, "col_grid");
+    return launch_p(c, "reed_sim_phys", col_grid(g.nx * g.ny), 0, kf);
+  };
+  auto alt = [&](auto Cn) -> int {   // hydrostatic is read only where reed_alt_mxg builds zint
+    if (!p->reed_alt_mxg) return go(Cn, std::false_type{}, std::true_type{});
+    if (p->hydrostatic) return go(Cn, std::true_type{}, std::true_type{});
+    return go(Cn, std::true_type{}, std::false_type{});
+  };
+  if (p->do_reed_cond) RT(alt(std::true_type{}));
+  else RT(alt(std::false_type{}));
+  return 0;
+}
+
+extern "C" int fv3_grid_upload_terminator(fv3_ctx *c, const double *agrid, double pi) {
+  if (!c || !agrid) return fail("fv3_grid_upload_terminator: null argument");
+  if (!c->grid_ready) return fail("fv3_grid_upload_terminator: context has no grid");
+  if (!(pi > 0.)) return fail("fv3_grid_upload_terminator: pi = %g <= 0", pi);
+  const size_t n2 = c->g.nA();
+  const double lc = 5. * pi / 3., thc = pi / 9.;   // fv_phys.F90:2840-2846
+  const double sinthc = std::sin(thc), costhc = std::cos(thc);
+  std::vector<double> k1(n2);
+  for (size_t n = 0; n < n2; n++) {
+    const double lon = agrid[n], lat = agrid[n2 + n];
+    k1[n] = std::fmax(0., std::sin(lat) * sinthc + std::cos(lat) * costhc * std::cos(lon - lc));   // :2873
+  }
+  if (c->term_k1) {
+    if (int rc = grp_flush_all()) return rc;
+    RT(rtf_sync(c->stream));
+  } else {
+    RT(rt_malloc((void **)&c->term_k1, n2 * sizeof(double)));
+  }
+  RT(rtf_h2d(c->term_k1, k1.data(), n2 * sizeof(double), c->stream));
+  RT(rtf_sync(c->stream));
+  return 0;
+}
+
+extern "C" int fv3_grid_download_terminator(fv3_ctx *c, double *k1) {
+  if (!c || !k1) return fail("fv3_grid_download_terminator: null argument");
+  if (!c->term_k1) return fail("fv3_grid_download_terminator: no k1 plane (fv3_grid_upload_terminator)");
+  RT(rtf_d2h(k1, c->term_k1, c->g.nA() * sizeof(double), c->stream));
+  RT(rtf_sync(c->stream));
+  return 0;
+}
+
+extern "C" int fv3_terminator_advance(fv3_ctx *c, int km, double pdt, int term_fill_negative, double *cl, double *cl2) {
+  FV3_ENTRY(c);
+  if (!c || !c->grid_ready) return fail("fv3_terminator_advance: context has no grid");
+  if (!cl || !cl2) return fail("fv3_terminator_advance: null field");
+  if (cl == cl2) return fail("fv3_terminator_advance: Cl and Cl2 are the same plane");
+  if (km < 1) return fail("fv3_terminator_advance: km = %d < 1", km);
+  if (!(pdt > 0.)) return fail("fv3_terminator_advance: pdt = %g <= 0", pdt);
+  if (!c->term_k1) return fail("fv3_terminator_advance: no k1 plane (fv3_grid_upload_terminator)");
+  const size_t n2 = c->g.nA();
+  TerminatorAdvance kf{n2 * (size_t)km, n2, term_fill_negative ? 1 : 0, pdt, 1. / pdt, c->term_k1, cl, cl2};
+  Dim3 grid;
+  grid.x = (unsigned)((kf.n + TerminatorAdvance::CH - 1) / TerminatorAdvance::CH);
+  grid.y = 1;
+  grid.z = 1;
+  RT(launch_p(c, "terminator_advance", grid, 0, kf));
   return 0;
 }
 

@@ -29,6 +29,8 @@ module fv3_mi355x_mod
   public :: fv3_interpolate_vertical
   public :: fv3_fv_update_phys, fv3_update_phys_params
   public :: fv3_grid_upload_lat, fv3_held_suarez_tend, fv3_held_suarez_params, fv3_age_of_air
+  public :: fv3_grid_upload_reed, fv3_reed_sim_phys, fv3_reed_consts, fv3_reed_params, fv3_grid_upload_terminator, fv3_terminator_advance
+  public :: fv3_grid_download_reed, fv3_grid_download_terminator
 
   type, bind(C) :: fv3_domain
     integer(c_int) :: is, ie, js, je, ng, npx, npy, npz, grid_type
@@ -117,6 +119,19 @@ module fv3_mi355x_mod
     real(c_double) :: rd_zur = 0.04_c_double
     integer(c_int) :: fresh = 0
     real(c_double) :: radius, pi
+  end type
+
+  type, bind(C) :: fv3_reed_consts          ! what reed_sim_physics and its wrapper read of constants_mod and gfdl_mp_mod (c_liq)
+    real(c_double) :: grav, rdgas, rvgas, cp_air, cp_vapor, c_liq, hlv, radius, omega, pi
+  end type
+
+  type, bind(C) :: fv3_reed_params          ! reed_sim_physics (driver/solo/fv_phys.F90:551-602, :2332): pdt, hydrostatic (read with
+    real(c_double) :: pdt                   ! reed_alt_mxg), reed_test 0 / 1 / 2, the three namelist switches, fresh /= 0: the four
+    integer(c_int) :: hydrostatic = 1       ! tendencies are taken as zero, not read, and written everywhere
+    integer(c_int) :: reed_test = 0
+    integer(c_int) :: do_reed_cond = 1, reed_cond_only = 0, reed_alt_mxg = 0
+    integer(c_int) :: fresh = 0
+    type(fv3_reed_consts) :: k
   end type
 
   type, bind(C) :: fv3_grid_dwinds    ! what update_dwinds_phys reads of the gridstruct on the sphere (fv_grid_utils.F90:3314-3326):
@@ -727,6 +742,46 @@ module fv3_mi355x_mod
       type(c_ptr), value :: ctx, pe, q
       integer(c_int), value :: km
       real(c_double), value :: time
+    end function
+    ! what reed_sim_physics reads of the gridstruct: lat = agrid(is:ie, js:je, 2), HOST, contiguous; once per context and reed_test
+    integer(c_int) function fv3_grid_upload_reed(ctx, lat, reed_test, k) bind(C, name="fv3_grid_upload_reed")
+      import :: c_int, c_ptr, fv3_reed_consts
+      type(c_ptr), value :: ctx, lat
+      integer(c_int), value :: reed_test
+      type(fv3_reed_consts), intent(in) :: k
+    end function
+    ! the planes the two uploads formed, back on the host, for checks: tab (is:ie, js:je, 2); k1 (isd:ied, jsd:jed)
+    integer(c_int) function fv3_grid_download_reed(ctx, tab) bind(C, name="fv3_grid_download_reed")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, tab
+    end function
+    integer(c_int) function fv3_grid_download_terminator(ctx, k1) bind(C, name="fv3_grid_download_terminator")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, k1
+    end function
+    ! the column loop of do_reed_sim_phys with reed_sim_physics inside it (driver/solo/fv_phys.F90:551-602, :2332-2817): the tendencies
+    ! added to u_dt, v_dt (A x npz), t_dt and q_dt = c_loc(q_dt(is, js, 1, sphum)) (is:ie, js:je, npz); q = c_loc(q(isd, jsd, 1, sphum));
+    ! rain (is:ie, js:je) written with do_reed_cond; delz may be c_null_ptr when hydrostatic.  The caller goes on with
+    ! fv3_terminator_advance, where the case has it, and fv3_fv_update_phys
+    integer(c_int) function fv3_reed_sim_phys(ctx, p, delp, pt, ua, va, q, pe, peln, phis, delz, u_dt, v_dt, t_dt, q_dt, rain) &
+        bind(C, name="fv3_reed_sim_phys")
+      import :: c_int, c_ptr, fv3_reed_params
+      type(c_ptr), value :: ctx, delp, pt, ua, va, q, pe, peln, phis, delz, u_dt, v_dt, t_dt, q_dt, rain
+      type(fv3_reed_params), intent(in) :: p
+    end function
+    ! what DCMIP2016_terminator_advance reads of the gridstruct: agrid (isd:ied, jsd:jed, 2), HOST; pi: constants_mod's
+    integer(c_int) function fv3_grid_upload_terminator(ctx, agrid, pi) bind(C, name="fv3_grid_upload_terminator")
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: ctx, agrid
+      real(c_double), value :: pi
+    end function
+    ! DCMIP2016_terminator_advance (driver/solo/fv_phys.F90:2819-2894): cl = c_loc(q(isd, jsd, 1, Cl)), cl2 = c_loc(q(isd, jsd, 1, Cl2)),
+    ! halo included; the reference's delp is never read and is not part of the call
+    integer(c_int) function fv3_terminator_advance(ctx, km, pdt, term_fill_negative, cl, cl2) bind(C, name="fv3_terminator_advance")
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: ctx, cl, cl2
+      integer(c_int), value :: km, term_fill_negative
+      real(c_double), value :: pdt
     end function
     ! interpolate_vertical (tools/fv_diagnostics.F90:4910-4948): a3 (km layers) at the pressure plev [Pa] into a2 (is:ie, js:je).
     ! in_ng = 0: a3 on the compute domain, as the reference's argument; in_ng = ng: a state field with its halo, in the place of the

@@ -268,6 +268,53 @@ class FvDynamics:
         self.atmosphere_step(bdt)
         self.held_suarez(bdt, **hs)
 
+    # -- Reed-Jablonowski simple physics ----------------------------------------------------------------------------
+    def reed_sim_phys(self, dt: float, reed_test: int = 0, do_reed_cond: bool = True, reed_cond_only: bool = False,
+                      reed_alt_mxg: bool = False, terminator=None, term_fill_negative: bool = False, consts: dict | None = None):
+        """the do_reed_sim_phys path of fv_phys (driver/solo/fv_phys.F90:292-313, :546-602, :654-658, :675-687) on the resident state, a
+        tile or the six faces alike, in the reference's order: reed_sim_physics with fresh set writes d["u_dt"], d["v_dt"], d["t_dt"]
+        and the sphum plane of d["q_dt"] (the reference zeroes the four first) and, with do_reed_cond, d["rain"];
+        DCMIP2016_terminator_advance when terminator = (Cl, Cl2), 1-based tracer indices, is given; fv_update_phys applies the
+        tendencies with the resident q_dt (moist_phys true).  The other planes of q_dt are zeroed once, where it is allocated.  No
+        field leaves the device."""
+        d, ctx, fl = self.dc.d, self.ctx, self.fl
+        npz = ctx.npz
+        if not self.nq:
+            raise ValueError("FvDynamics.reed_sim_phys: no tracer (reed_sim_physics reads q(:,:,:,sphum))")
+        sphum = self.sg_species.get("sphum", 0) or 1
+        if terminator is not None:
+            cl, cl2 = (int(t) for t in terminator)
+            if not (1 <= cl <= self.nq and 1 <= cl2 <= self.nq and cl != cl2):
+                raise ValueError(f"FvDynamics.reed_sim_phys: terminator = {terminator} are not two tracers of 1..{self.nq}")
+        if "t_dt" not in d:
+            d["t_dt"] = ctx.empty("CC", npz)
+        for n in ("u_dt", "v_dt"):
+            if n not in d:
+                d[n] = ctx.zeros("A", npz)                                 # (the halo: fv_update_phys' exchange fills it)
+        if "q_dt" not in d:
+            d["q_dt"] = ctx.from_host(np.zeros((ctx.bd.nx, ctx.bd.ny, npz, self.nq), order="F"))
+        if "rain" not in d:
+            d["rain"] = ctx.zeros("CC")
+        faces = list(enumerate(ctx.ctxs)) if hasattr(ctx, "ctxs") else [(None, ctx)]
+        at = lambda a, t: a if t is None else a[t]      # noqa: E731
+        for t, c in faces:
+            c.reed_sim_phys(dt, at(d["delp"], t), at(d["pt"], t), at(d["ua"], t), at(d["va"], t), _TracerView(at(d["q"], t), sphum - 1),
+                            at(d["pe"], t), at(d["peln"], t), at(d["phis"], t), None if fl.hydrostatic else at(d["delz"], t), at(d["u_dt"], t),
+                            at(d["v_dt"], t), at(d["t_dt"], t), _TracerView(at(d["q_dt"], t), sphum - 1), at(d["rain"], t),
+                            hydrostatic=fl.hydrostatic, reed_test=reed_test, do_reed_cond=do_reed_cond, reed_cond_only=reed_cond_only,
+                            reed_alt_mxg=reed_alt_mxg, fresh=True, consts=dict(dict(self.neg_adj_consts, radius=self.radius), **(consts or {})))
+        if terminator is not None:                                         # :654-658
+            for t, c in faces:
+                c.terminator_advance(npz, dt, _TracerView(at(d["q"], t), cl - 1), _TracerView(at(d["q"], t), cl2 - 1),
+                                     term_fill_negative=term_fill_negative)
+        self.fv_update_phys(dt, d["t_dt"], d["q_dt"], d["u_dt"], d["v_dt"])
+
+    def moist_forced_step(self, bdt: float, **reed):
+        """atmosphere_step followed by reed_sim_phys: one step of a moist idealised run (the solo driver's atmosphere_dynamics and fv_phys
+        with do_reed_sim_phys)"""
+        self.atmosphere_step(bdt)
+        self.reed_sim_phys(bdt, **reed)
+
     # -- neg_adj3 -------------------------------------------------------------------------------------------------
     def _prt_negative(self, when: str):
         """prt_negative (fv_sg.F90:1372-1392) of T and the six species: the global minimum, reported when below its threshold"""

@@ -38,7 +38,9 @@ EXPORTS = ["fv3_last_error", "fv3_create", "fv3_destroy", "fv3_set_stream", "fv3
            "fv3_p_grad_c", "fv3_nh_p_grad", "fv3_split_p_grad", "fv3_grad1_p_update", "fv3_d_sw_inline_q", "fv3_flux_accum", "fv3_fill2d_mass", "fv3_fill2d_apply", "fv3_set_remap_te", "fv3_profile_report_timers", "fv3_prt_maxmin", "fv3_pk3_halo", "fv3_pe_halo", "fv3_geopk", "fv3_zh_from_delz", "fv3_set_ak_bk", "fv3_set_moist", "fv3_lagrangian_to_eulerian",
            "fv3_tracer_2d_prep", "fv3_tracer_2d_scale", "fv3_tracer_2d_step", "fv3_neg_adj3",
            "fv3_fv_subgrid_z", "fv3_grid_upload_dwinds", "fv3_update_dwinds_phys", "fv3_interpolate_vertical", "fv3_fv_update_phys",
-           "fv3_grid_upload_lat", "fv3_held_suarez_tend", "fv3_age_of_air"]
+           "fv3_grid_upload_lat", "fv3_held_suarez_tend", "fv3_age_of_air",
+           "fv3_grid_upload_reed", "fv3_grid_download_reed", "fv3_reed_sim_phys", "fv3_grid_upload_terminator", "fv3_grid_download_terminator",
+           "fv3_terminator_advance"]
 
 
 class Fv3Error(RuntimeError):
@@ -168,6 +170,25 @@ class _UpdatePhysParams(C.Structure):
 class _HeldSuarezParams(C.Structure):
     _fields_ = [("pdt", C.c_double), ("strat", C.c_int), ("zurita", C.c_int), ("rd_zur", C.c_double), ("fresh", C.c_int),
                 ("radius", C.c_double), ("pi", C.c_double)]
+
+
+class _ReedConsts(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ["grav", "rdgas", "rvgas", "cp_air", "cp_vapor", "c_liq", "hlv", "radius", "omega", "pi"]]
+
+
+class _ReedParams(C.Structure):
+    _fields_ = [("pdt", C.c_double)] + [(n, C.c_int) for n in ["hydrostatic", "reed_test", "do_reed_cond", "reed_cond_only", "reed_alt_mxg",
+                                                                "fresh"]] + [("k", _ReedConsts)]
+
+
+# what reed_sim_physics and its wrapper (driver/solo/fv_phys.F90:74-85, :546-602, :2516-2520) take from constants_mod and gfdl_mp_mod
+REED_CONSTS = dict(grav=GRAV, rdgas=RDGAS, rvgas=461.50, cp_air=CP_AIR, cp_vapor=4.0 * 461.50, c_liq=4.218e3, hlv=2.500e6, radius=6.3712e6,
+                   omega=7.2921e-5, pi=3.14159265358979323846)
+
+
+def _reed_consts(consts):
+    k = dict(REED_CONSTS, **{n: v for n, v in (consts or {}).items() if n in REED_CONSTS})
+    return _ReedConsts(*(float(k[n]) for n, _ in _ReedConsts._fields_))
 
 
 SG_SPECIES = ("sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel")
@@ -555,6 +576,71 @@ class Context:
         """age_of_air (driver/solo/hswf.F90:209-245): the age tracer q (ONE tracer, A x km) zeroed when time < 1e-6, else set to
         5e-6 / 60 * time where pe(i, k, j) >= 75000 Pa"""
         self.lib.check(self.lib.dll.fv3_age_of_air(self.h, C.c_int(int(km)), C.c_double(float(time)), _pp(pe), _pp(q)), "fv3_age_of_air")
+
+    def grid_upload_reed(self, reed_test=0, lat=None, consts=None):
+        """fv3_grid_upload_reed: Tsurf and the SST factor of qsats (driver/solo/fv_phys.F90:2571-2586, :2719) on the compute domain, formed
+        on the host from the latitude of the cell centres, agrid(is:ie, js:je, 2), for one reed_test.  Default: the gridstruct's agrid.
+        consts: overrides of REED_CONSTS."""
+        if lat is None:
+            if "agrid" not in self.grid.m:
+                raise Fv3Error("grid_upload_reed: the gridstruct has no agrid")
+            b = self.bd
+            lat = b.view(np.asarray(self.grid.m["agrid"])[..., 1], "A", b.is_, b.ie, b.js, b.je)
+        lat = np.asfortranarray(lat, dtype=np.float64)
+        if lat.shape != (self.bd.nx, self.bd.ny):
+            raise Fv3Error(f"grid_upload_reed: lat has the shape {lat.shape}, the compute domain {(self.bd.nx, self.bd.ny)}")
+        k = _reed_consts(consts)
+        self.lib.check(self.lib.dll.fv3_grid_upload_reed(self.h, lat.ctypes.data_as(_dp), C.c_int(int(reed_test)), C.byref(k)), "fv3_grid_upload_reed")
+        self.reed_ready = int(reed_test)
+
+    def grid_download_reed(self):
+        """fv3_grid_download_reed -> (Tsurf, the SST factor of qsats), each (is:ie, js:je), as fv3_grid_upload_reed formed them"""
+        tab = np.zeros((self.bd.nx, self.bd.ny, 2), order="F")
+        self.lib.check(self.lib.dll.fv3_grid_download_reed(self.h, tab.ctypes.data_as(_dp)), "fv3_grid_download_reed")
+        return np.asfortranarray(tab[..., 0]), np.asfortranarray(tab[..., 1])
+
+    def reed_sim_phys(self, pdt, delp, pt, ua, va, q, pe, peln, phis, delz, u_dt, v_dt, t_dt, q_dt, rain, hydrostatic=True, reed_test=0,
+                      do_reed_cond=True, reed_cond_only=False, reed_alt_mxg=False, fresh=False, consts=None):
+        """the column loop of do_reed_sim_phys with reed_sim_physics inside it (driver/solo/fv_phys.F90:551-602, :2332-2817): the
+        tendencies of the Reed-Jablonowski simple physics added to u_dt, v_dt (A x npz), t_dt and q_dt, the sphum plane of the
+        tendency array (is:ie, js:je, npz; no halo); rain (is:ie, js:je) is written with do_reed_cond.  q: the sphum tracer (A x npz);
+        delz may be None when hydrostatic.  fresh: the incoming tendencies are taken as zero, not read, and every cell of the four
+        on the compute domain is written.  The table is uploaded from the gridstruct on first use of a reed_test."""
+        if getattr(self, "reed_ready", None) is None:
+            self.grid_upload_reed(reed_test, consts=consts)
+        pr = _ReedParams(float(pdt), int(bool(hydrostatic)), int(reed_test), int(bool(do_reed_cond)), int(bool(reed_cond_only)),
+                         int(bool(reed_alt_mxg)), int(bool(fresh)), _reed_consts(consts))
+        self.lib.check(self.lib.dll.fv3_reed_sim_phys(self.h, C.byref(pr), _pp(delp), _pp(pt), _pp(ua), _pp(va), _pp(q), _pp(pe), _pp(peln),
+                                                      _pp(phis), _pp(delz), _pp(u_dt), _pp(v_dt), _pp(t_dt), _pp(q_dt), _pp(rain)),
+                       "fv3_reed_sim_phys")
+
+    def grid_upload_terminator(self, agrid=None, pi=REED_CONSTS["pi"]):
+        """fv3_grid_upload_terminator: k1 of DCMIP2016_terminator_advance (driver/solo/fv_phys.F90:2873) over the A layout, formed on the
+        host from agrid (A x 2: longitude, latitude).  Default: the gridstruct's agrid."""
+        if agrid is None:
+            if "agrid" not in self.grid.m:
+                raise Fv3Error("grid_upload_terminator: the gridstruct has no agrid")
+            agrid = self.grid.m["agrid"]
+        agrid = np.asfortranarray(agrid, dtype=np.float64)
+        if agrid.shape != self.bd.shape("A") + (2,):
+            raise Fv3Error(f"grid_upload_terminator: agrid has the shape {agrid.shape}, the A layout x 2 is {self.bd.shape('A') + (2,)}")
+        self.lib.check(self.lib.dll.fv3_grid_upload_terminator(self.h, agrid.ctypes.data_as(_dp), C.c_double(float(pi))),
+                       "fv3_grid_upload_terminator")
+        self.terminator_ready = True
+
+    def grid_download_terminator(self):
+        """fv3_grid_download_terminator -> k1 over the A layout, as fv3_grid_upload_terminator formed it"""
+        k1 = np.zeros(self.bd.shape("A"), order="F")
+        self.lib.check(self.lib.dll.fv3_grid_download_terminator(self.h, k1.ctypes.data_as(_dp)), "fv3_grid_download_terminator")
+        return k1
+
+    def terminator_advance(self, km, pdt, cl, cl2, term_fill_negative=False):
+        """DCMIP2016_terminator_advance (driver/solo/fv_phys.F90:2819-2894) on the tracer planes Cl and Cl2 (A x km each), halo included.
+        The k1 plane is uploaded from the gridstruct on first use."""
+        if not getattr(self, "terminator_ready", False):
+            self.grid_upload_terminator()
+        self.lib.check(self.lib.dll.fv3_terminator_advance(self.h, C.c_int(int(km)), C.c_double(float(pdt)), C.c_int(int(bool(term_fill_negative))),
+                                                           _pp(cl), _pp(cl2)), "fv3_terminator_advance")
 
     def interpolate_vertical(self, km, plev, peln, a3, a2, in_ng=0):
         """interpolate_vertical (tools/fv_diagnostics.F90:4910-4948): a2 (is:ie, js:je) = a3 (km layers) at the pressure plev [Pa], linear

@@ -772,8 +772,8 @@ int fv3_grid_upload_lat(fv3_ctx *ctx, const double *lat);
  * pi <= 0; no latitude table uploaded.
  * Not defined, because the reference is not: a column whose bottom layer already has pl <= 100e2 with strat -- the reference reads
  * pl(npz+1) and teq(npz+1) there.
- * Not built: the rest of fv_phys.F90 (do_surf_drag, Reed physics, the mixed layer, the gray radiation, the terminator chemistry, the
- * clock tracers), send_data, the regional / nested paths. */
+ * Not built: the rest of fv_phys.F90 (do_surf_drag, the mixed layer, the gray radiation, the clock tracers; the Reed physics and the
+ * terminator chemistry are fv3_reed_sim_phys and fv3_terminator_advance), send_data, the regional / nested paths. */
 typedef struct fv3_held_suarez_params {
   double pdt;            /* the physics step [s] */
   int strat, zurita;     /* do_strat_HS_forcing, do_zurita_HS */
@@ -791,6 +791,84 @@ int fv3_held_suarez_tend(fv3_ctx *ctx, const fv3_held_suarez_params *p, const do
  * fv3_group: one).  Written: q on the compute domain, the cells named above; the halo keeps its bits.  Refused: null fields,
  * km < 1, time not a number. */
 int fv3_age_of_air(fv3_ctx *ctx, int km, double time, const double *pe, double *q);
+
+/* fv3_grid_upload_reed -- what reed_sim_physics reads of the gridstruct, agrid(is:ie, js:je, 2) (driver/solo/fv_phys.F90:585,
+ * :2571-2586, :2719): lat is the latitude [rad] of the cell centres on the compute domain, (is:ie, js:je), HOST.  The host forms two
+ * planes with its libm, each in the reference's own expression, and uploads them: Tsurf (:2573-2577 for reed_test = 1, SST_tc =
+ * 302.15 for 0, 1.E25 for 2) and the SST factor of qsats, exp((dc_vap*log(Tsurf/tice) + Lv0*(Tsurf-tice)/(Tsurf*tice))/rvgas) (:2719)
+ * with tice, dc_vap = cp_vapor - c_liq and Lv0 = hlv - dc_vap*tice of :75-85 -- no sin, cos or pow of the latitude runs on the
+ * device.  Read of k: rdgas, rvgas, cp_vapor, c_liq, hlv, radius, omega, pi.  Written: the context's table and the reed_test it
+ * belongs to, nothing else.  Refused: null arguments, a context without a grid, reed_test outside 0, 1, 2, a constant of grav,
+ * rdgas, rvgas, cp_air, radius, pi that is not positive.  A second call replaces the table (queued launches of an fv3_group run
+ * first). */
+typedef struct fv3_reed_consts {
+  double grav, rdgas, rvgas, cp_air, cp_vapor;   /* constants_mod's */
+  double c_liq;                                  /* gfdl_mp.F90:137 */
+  double hlv, radius, omega, pi;                 /* constants_mod's */
+} fv3_reed_consts;
+int fv3_grid_upload_reed(fv3_ctx *ctx, const double *lat, int reed_test, const fv3_reed_consts *k);
+/* fv3_grid_download_reed -- the two planes fv3_grid_upload_reed formed, back on the host: tab (is:ie, js:je, 2), HOST -- Tsurf, then the
+ * SST factor.  For checks: the planes are held bit for bit to the reference's compiler.  Refused: null arguments, no table. */
+int fv3_grid_download_reed(fv3_ctx *ctx, double *tab);
+
+/* fv3_reed_sim_phys -- the column loop of the solo driver's do_reed_sim_phys branch, driver/solo/fv_phys.F90:551-602, with
+ * reed_sim_physics (:2332-2817) inside it: the Reed-Jablonowski simple physics, whose tendencies go to fv_update_phys with
+ * moist_phys true (:675-687; fv3_fv_update_phys).  One launch (six faces of an fv3_group: one), one thread per column.  The
+ * wrapper's arithmetic (:555-580): q2 = max(0, q), pm = dp / (peln(k+1) - peln(k)), rdelp = 1 / dp, zint upwards from phis / grav
+ * (hydrostatic: with the UNCLAMPED q, :570; else minus delz); zint is read only with reed_alt_mxg.  The routine: za of the bottom
+ * level from log(pe) (:2562-2563); with do_reed_cond the large-scale condensation (:2608-2632) and its rain; unless reed_cond_only
+ * (:2635) the drag coefficients (:2654-2705; reed_alt_mxg: the height form of :2660-2678), the implicit surface fluxes at the
+ * bottom level (:2717-2733) and the implicit boundary-layer diffusion of u, v, theta, q (:2743-2815): a sweep up the column leaves
+ * CE, CEm, CFu, CFv, CFt, CFq per level in a work array of the context (6 x (is:ie, js:je, npz); the reference's level pver+1 is
+ * zero and stays in registers), the sweep down reads them.  The work array is under the poison contract (FV3_MI355X_POISON): filled
+ * at the head of the call, written before it is read, nothing carried between calls.  log, exp are include/fv3_math.h, x**y with
+ * a real y is exp of y log x from the same header, sqrt is correctly rounded; the scalars of :74-85, :548-549, :2516-2551 are formed on the host
+ * in the reference's expressions from the constants in k.
+ * fresh /= 0: the incoming u_dt, v_dt, t_dt and q_dt are taken as zero and not read, and every cell of the four on the compute
+ * domain is written -- bit-identical, the sign of zero included, with zeroing them and calling with fresh = 0.
+ * delp, pt (the temperature), ua, va, u_dt, v_dt: A x npz; q: the sphum tracer, A x npz; phis: A; t_dt, delz (is:ie, js:je, npz) and
+ * q_dt, the sphum PLANE of the tendency array (is:ie, js:je, npz): NO halo; pe (is-1:ie+1, npz+1, js-1:je+1); peln (is:ie, npz+1,
+ * js:je); rain (is:ie, js:je).  Device pointers.  delz may be NULL when hydrostatic.
+ * Written, on the compute domain only: u_dt, v_dt, t_dt, q_dt (each the incoming value plus the routine's tendency); rain =
+ * rain2 * 8.64e7 [mm/d] only with do_reed_cond.  Nothing else: halos, the other planes of the caller's q_dt and every input keep
+ * their bits.
+ * Refused (status 1 and a message, nothing launched): null fields; npz < 1; pdt <= 0; reed_test outside 0, 1, 2; no Reed table
+ * uploaded (fv3_grid_upload_reed), or one uploaded for another reed_test; delz NULL when not hydrostatic; a constant of grav, rdgas,
+ * rvgas, cp_air, radius, pi that is not positive.
+ * Not defined, because the reference is not: reed_test = 2 -- the reference returns at :2506 with its intent(out) tendencies
+ * undefined and the wrapper then adds them.  The library leaves the four tendencies alone there (with fresh it writes zeros) and,
+ * with do_reed_cond, writes rain = 0.
+ * Not built: send_data, prec_total and its g_sum (:603-616), the USE_REED_CONST and SIM_NGGPS builds, everything else in
+ * fv_phys.F90. */
+typedef struct fv3_reed_params {
+  double pdt;                                        /* the physics step [s] */
+  int hydrostatic;                                   /* read only with reed_alt_mxg */
+  int reed_test;                                     /* 0: tropical cyclone (5-1), 1: moist baroclinic wave (4-3), 2: no physics */
+  int do_reed_cond, reed_cond_only, reed_alt_mxg;
+  int fresh;                                         /* /= 0: the four tendencies are taken as zero, not read, and written everywhere */
+  fv3_reed_consts k;
+} fv3_reed_params;
+int fv3_reed_sim_phys(fv3_ctx *ctx, const fv3_reed_params *p, const double *delp, const double *pt, const double *ua, const double *va,
+                      const double *q, const double *pe, const double *peln, const double *phis, const double *delz, double *u_dt,
+                      double *v_dt, double *t_dt, double *q_dt, double *rain);
+
+/* fv3_grid_upload_terminator -- what DCMIP2016_terminator_advance reads of the gridstruct (driver/solo/fv_phys.F90:655-657, :2873):
+ * agrid, the A layout x 2 (longitude, latitude [rad]), HOST.  The host forms ONE plane over the A layout, halo included, with its
+ * libm in the reference's expression, k1 = max(0., sin(lat)*sinthc + cos(lat)*costhc*cos(lon - lc)) with lc = 5 pi / 3, thc = pi / 9,
+ * and uploads it.  pi: constants_mod's.  Refused: null arguments, a context without a grid, pi <= 0. */
+int fv3_grid_upload_terminator(fv3_ctx *ctx, const double *agrid, double pi);
+/* fv3_grid_download_terminator -- the k1 plane fv3_grid_upload_terminator formed, back on the host: k1 over the A layout, HOST.  For
+ * checks.  Refused: null arguments, no plane. */
+int fv3_grid_download_terminator(fv3_ctx *ctx, double *k1);
+
+/* fv3_terminator_advance -- DCMIP2016_terminator_advance, driver/solo/fv_phys.F90:2819-2894, the chlorine chemistry the DCMIP-2016
+ * cases run behind the physics (:654-658).  Pointwise over the WHOLE tracer planes, halo included, as the reference loops
+ * (ifirst:ilast, jfirst:jlast), km levels; cl, cl2: the tracer planes Cl and Cl2, A x km each, device pointers.  With
+ * term_fill_negative first the repair of :2857-2859.  sqrt is correctly rounded, exp is include/fv3_math.h.  One launch (six faces of
+ * an fv3_group: one).  Written: cl, cl2.  The reference's delp is an argument its routine never reads: not part of the call.
+ * Refused: null fields, cl == cl2, km < 1, pdt <= 0, no k1 plane uploaded.  Not defined, as in the reference: a cell with
+ * r*r + 2 r (Cl + 2 Cl2) < 0 (the square root of a negative number). */
+int fv3_terminator_advance(fv3_ctx *ctx, int km, double pdt, int term_fill_negative, double *cl, double *cl2);
 
 /* fv3_interpolate_vertical -- interpolate_vertical, tools/fv_diagnostics.F90:4910-4948 (call sites :2017 the 850 hPa vorticity, :2198 and :2263-2299
  * the relative humidity at 200 hPa and at ten CMIP levels, :2971-2979 condensate at 200 / 500 / 850 hPa, :3522): the field a3 (km layers) at the one pressure plev [Pa], linear in the layer-mean log pressure
