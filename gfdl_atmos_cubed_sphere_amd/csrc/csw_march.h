@@ -33,7 +33,7 @@ inline MarchDims make_csw_dims(const Grid &g, int tj) {
   d.tj = tj;
   d.klist = nullptr;
   d.nk = 0;
-  d.k_fast = march_k_fast();
+  d.k_fast = 0;
   d.nstrips = (g.nx + 4 + kCswCols - 1) / kCswCols;
   d.nsegs = (g.ny + 4 + tj - 1) / tj;
   d.alt_nk = d.alt_ng = d.alt_tj = 0;

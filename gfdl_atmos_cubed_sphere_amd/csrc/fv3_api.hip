@@ -138,7 +138,6 @@ struct fv3_ctx {
   fv3_cube_field cube_pend[FV3_HALO_MAX_FIELDS] = {};
   size_t cube_roff[FV3_HALO_MAX_FIELDS][6] = {};
   fv3_halo_field pend_fields[FV3_HALO_MAX_FIELDS] = {};
-  int col_pool = 0;      // workgroups of the pooled launches of the column solvers (0: one workgroup per 256 columns)
   int cubed_frame = 4;   // cubed-sphere hybrid: width of the frame the pass kernels own (0: passes on the whole face)
   int cubed_reach = 5;   // ... and how much wider the frame of the passes' intermediates is
   int cubed_frame_c = 7; // the frame of c_sw (d2a2c_vect has its edge forms within 4 points of an edge)
@@ -179,11 +178,9 @@ struct fv3_ctx {
   int march_tj_fused = kMarchTj;   // rows per segment of the fused d_sw kernels, transports and momentum (FV3_MI355X_MARCH_TJ_FUSED)
   int trc_nt = 3;  // tracers per wavefront in the sub-cycle kernel (FV3_MI355X_TRACER_NT: 1..4, default 3)
   int remap_nt = 3;  // tracers per thread in the remap (FV3_MI355X_REMAP_NT: 1..3, default 3)
-  int riem_blocked = 1;   // the same for the Riemann solvers' four slabs (FV3_MI355X_RIEM_SCR: 0 / 1, default 1)
   int pgrad_fused = 1;    // nh_p_grad as ONE kernel where the domain has no face edges (NhPGradFused; FV3_MI355X_PGRAD_FUSED=0: a2b_ord4 + the gradient)
   int riem_lds = 1;       // the dry SIM1 Riemann solvers with the levels across the lanes, BIT-IDENTICAL to the slab kernels (nh_fast.h
                           // RiemFast<CG, true>; FV3_MI355X_RIEM_LDS: 0 / 1, default 1)
-  int remap_blocked = 1;  // scratch slabs of the remap in per-wavefront blocks (FV3_MI355X_REMAP_SCR: 0 / 1, default 1)
   int remap_lds = 1;      // the remap with the column in LDS (remap_fast.h; bit-identical to the slab kernels) where it is built for the
                           // configuration (FV3_MI355X_REMAP_LDS: 0 / 1, default 1)
   int tj_fixed = 0;          // FV3_MI355X_MARCH_TJ_FUSED is set: take the rows per segment as given (seg_rows)
@@ -638,9 +635,6 @@ static void ctx_switches(fv3_ctx *c) {
   c->tj_fixed = c->tj_env_fused = tj_set;
   c->trc_nt = env_int("FV3_MI355X_TRACER_NT", 3); if (c->trc_nt < 1 || c->trc_nt > 4) c->trc_nt = 3;
   c->remap_nt = env_int("FV3_MI355X_REMAP_NT", 3); if (c->remap_nt < 1 || c->remap_nt > RemapFields::kGroupMax) c->remap_nt = 3;
-  c->riem_blocked = env_int("FV3_MI355X_RIEM_SCR", 1) != 0;
-  c->remap_blocked = env_int("FV3_MI355X_REMAP_SCR", 1) != 0;
-  c->col_pool = env_int("FV3_MI355X_COL_POOL", 0); if (c->col_pool < 0) c->col_pool = 0;
   c->pgrad_fused = env_int("FV3_MI355X_PGRAD_FUSED", 1) != 0;
   c->riem_lds = env_int("FV3_MI355X_RIEM_LDS", 1) != 0;
   c->remap_lds = env_int("FV3_MI355X_REMAP_LDS", 1);   // 0: slab kernels, 1: the LDS kernels where they pay (fv3_lagrangian_to_eulerian), 2: wherever built
@@ -3225,11 +3219,6 @@ static int need_scratch(fv3_ctx *c, int n) {
   return 0;
 }
 
-// pooled column launch (FV3_COL_FOR_POOL): pool workgroups, or one per column block when there are fewer blocks / no pool
-static int col_pool(const fv3_ctx *c, int ncol) {
-  const int nb = (ncol + 255) / 256;
-  return (c->col_pool > 0 && c->riem_blocked && nb > c->col_pool) ? c->col_pool : 0;
-}
 static Dim3 col_grid(int ncol) {
   Dim3 gr;
   gr.x = (unsigned)((ncol + 255) / 256);
@@ -3381,21 +3370,20 @@ extern "C" int fv3_riem_solver_c(fv3_ctx *c, double dt, const fv3_nh_consts *cn,
     if (c->riem_lds) {         // the recurrences in the reference's order: the slab kernel's bits
       RiemFast<true, true> kf{c->g, c->g.npz, dt, to_consts(c, cn), hs, pt, delp, ws, const_cast<double *>(w3), gz,
                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pef, 0, 0, 0};
-      kf.probe = env_int("FV3_MI355X_RIEM_PROBE", 0);
       RT(launch_p2(c, "riem_solver_c", Dim3{(unsigned)kf.nblocks_x(), (unsigned)kf.nrows(), 1}, kf.kLdsDoubles, kf));
       return 0;
     }
   }
   if (need_scratch(c, 4)) return 1;
-  const int ncc = (c->g.nx + 2) * (c->g.ny + 2), pool = col_pool(c, ncc);
+  const int ncc = (c->g.nx + 2) * (c->g.ny + 2);
   if (c->q_con) {
     RiemSolverC<true> kf{c->g, c->g.npz, dt, to_consts(c, cn), hs, w3, pt, delp, ws, gz, pef,
-                         c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], c->q_con, c->cappa, c->riem_blocked, pool};
-    RT(launch_c(c, "riem_solver_c", pool ? col_grid(pool * 256) : col_grid(ncc), kf));
+                         c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], c->q_con, c->cappa};
+    RT(launch_c(c, "riem_solver_c", col_grid(ncc), kf));
   } else {
     RiemSolverC<false> kf{c->g, c->g.npz, dt, to_consts(c, cn), hs, w3, pt, delp, ws, gz, pef,
-                          c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], nullptr, nullptr, c->riem_blocked, pool};
-    RT(launch_c(c, "riem_solver_c", pool ? col_grid(pool * 256) : col_grid(ncc), kf));
+                          c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3], nullptr, nullptr};
+    RT(launch_c(c, "riem_solver_c", col_grid(ncc), kf));
   }
   return 0;
 }
@@ -3437,23 +3425,22 @@ extern "C" int fv3_riem_solver3(fv3_ctx *c, double dt, const fv3_nh_consts *cn, 
     if (c->riem_lds) {
       RiemFast<false, true> kf{c->g, c->g.npz, dt, to_consts(c, cn), zs, pt, delp, ws, w, zh, delz, ppe, pk3, pe, pk, peln, nullptr,
                                use_logp, last_call, fp_out};
-      kf.probe = env_int("FV3_MI355X_RIEM_PROBE", 0);
       RT(launch_p2(c, "riem_solver3", Dim3{(unsigned)kf.nblocks_x(), (unsigned)kf.nrows(), 1}, kf.kLdsDoubles, kf));
       return 0;
     }
   }
   if (need_scratch(c, 4)) return 1;
-  const int ncc = c->g.nx * c->g.ny, pool = col_pool(c, ncc);
+  const int ncc = c->g.nx * c->g.ny;
   if (c->q_con || c->cappa) {
     RiemSolver3<true> kf{c->g, c->g.npz, dt, to_consts(c, cn), zs, pt, delp, ws, w, delz, zh, pe, ppe, pk3, pk, peln,
                          use_logp, last_call, fp_out, c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3],
-                         c->q_con, c->cappa, c->riem_blocked, pool};
-    RT(launch_c(c, "riem_solver3", pool ? col_grid(pool * 256) : col_grid(ncc), kf));
+                         c->q_con, c->cappa, 1, 0};
+    RT(launch_c(c, "riem_solver3", col_grid(ncc), kf));
   } else {
     RiemSolver3<false> kf{c->g, c->g.npz, dt, to_consts(c, cn), zs, pt, delp, ws, w, delz, zh, pe, ppe, pk3, pk, peln,
                           use_logp, last_call, fp_out, c->scratch[0], c->scratch[1], c->scratch[2], c->scratch[3],
-                          nullptr, nullptr, c->riem_blocked, pool};
-    RT(launch_c(c, "riem_solver3", pool ? col_grid(pool * 256) : col_grid(ncc), kf));
+                          nullptr, nullptr, 1, 0};
+    RT(launch_c(c, "riem_solver3", col_grid(ncc), kf));
   }
   return 0;
 }
@@ -3472,7 +3459,7 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, int hord, const double *zs, const dou
   const int km = g.npz;
   double *cxa = c->scratch[0], *xfa = c->scratch[1], *cya = c->scratch[2], *yfa = c->scratch[3];
   if (c->riem_lds && km >= 3 && km <= 127) {   // levels across the lanes, the elimination in the reference's order: the slab kernel's bits
-    EdgeProfileLds kf{g, km, c->ec, c->edge_dev + 3 * km, crx, xfx, cxa, xfa, (int)g.nCX(), cry, yfx, cya, yfa, (int)g.nCY(),
+    EdgeProfileLds kf{g, km, c->ec, crx, xfx, cxa, xfa, (int)g.nCX(), cry, yfx, cya, yfa, (int)g.nCY(),
                       c->edge_dev + 4 * km};
     RT(launch_p2(c, "edge_profile", Dim3{(unsigned)kf.nblocks(), 1, 1}, 2 * kFBuf, kf));
   } else {
@@ -4053,7 +4040,7 @@ extern "C" int fv3_set_moist(fv3_ctx *c, const fv3_moist_params *m, double *q_co
 static int energy_par(fv3_ctx *c, const fv3_remap_params *p, RemapPar &rp, const char *who) {
   rp = RemapPar{p->last_step, p->hydrostatic, p->adiabatic, p->nq, p->kord_mt, p->kord_wz, p->kord_tm, p->sphum,
                 p->akap, p->ptop, p->rdgas, p->grav, p->cv_air, p->r_vir, p->cp, p->t_min,
-                0, 0, 0, 0, 0, 0, 0, 0, 0., 0., 0., nullptr, nullptr, p->fill, c->remap_blocked};
+                0, 0, 0, 0, 0, 0, 0, 0, 0., 0., 0., nullptr, nullptr, p->fill, 1};
   if (p->sphum < 0 || p->sphum > p->nq) return fail("%s: sphum out of range", who);
   if (c->moist_on && (c->moist.moist_kappa || c->moist.use_cond)) {
     const fv3_moist_params &m = c->moist;
@@ -4139,7 +4126,6 @@ extern "C" int fv3_set_remap_te(fv3_ctx *c, int remap_te, const double *hs, doub
   return 0;
 }
 
-static int remap_probe() { return env_int("FV3_MI355X_REMAP_PROBE", 0); }
 extern "C" int fv3_lagrangian_to_eulerian(fv3_ctx *c, const fv3_remap_params *p, const int *kord_tr, double *ps,
                                           double *pe, double *delp, double *pkz, double *pk, double *u, double *v,
                                           double *w, double *delz, double *pt, double *q, double *peln, double *omga,
@@ -4166,7 +4152,7 @@ extern "C" int fv3_lagrangian_to_eulerian(fv3_ctx *c, const fv3_remap_params *p,
   }
   RemapPar rp{p->last_step, p->hydrostatic, p->adiabatic, p->nq, p->kord_mt, p->kord_wz, p->kord_tm, p->sphum,
               p->akap, p->ptop, p->rdgas, p->grav, p->cv_air, p->r_vir, p->cp, p->t_min,
-              0, 0, 0, 0, 0, 0, 0, 0, 0., 0., 0., nullptr, nullptr, p->fill, c->remap_blocked};
+              0, 0, 0, 0, 0, 0, 0, 0, 0., 0., 0., nullptr, nullptr, p->fill, 1};
   const bool moist = c->moist_on && (c->moist.moist_kappa || c->moist.use_cond);
   if (moist) {
     const fv3_moist_params &m = c->moist;
@@ -4206,13 +4192,13 @@ extern "C" int fv3_lagrangian_to_eulerian(fv3_ctx *c, const fv3_remap_params *p,
         const Dim3 gr{(unsigned)((g.nx + kFC - 1) / kFC), (unsigned)g.ny, 1};
         if (p->hydrostatic) {
           using K = RemapFastScalars<true, false, L>;
-          RT((launch_p2<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga, remap_probe()}));
+          RT((launch_p2<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga}));
         } else if (moist) {   // use_cond / moist_kappa (fv3_set_moist): cappa from moist_cv in the temperature transform and in pkz
           using K = RemapFastScalars<false, true, L>;
-          RT((launch_p2<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga, remap_probe()}));
+          RT((launch_p2<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga}));
         } else {
           using K = RemapFastScalars<false, false, L>;
-          RT((launch_p2<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga, remap_probe()}));
+          RT((launch_p2<K>)(c, "remap_lds_scalars", gr, RLay<L>::Lds, K{g, km, rp, ak, bk, c->kord_tr_dev, pe, ws, ps, delp, pkz, pk, delz, pt, peln, w, q, omga}));
         }
       }
       {

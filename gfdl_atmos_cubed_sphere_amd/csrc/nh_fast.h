@@ -201,7 +201,7 @@ __device__ __forceinline__ vd row_shl1_v(vd a, vd fill) { return row_shl<1>(a, f
 // no 16-column block starts on a 128-byte line and neighbouring blocks share one; as neighbours in the launch they ran on different
 // XCDs and every shared line was fetched into two L2s (FETCH_SIZE 2.3 x the fields of Riem_Solver3, 2 x of the remap).  With this
 // permutation each XCD owns one contiguous range of blocks (the last nb mod 8 blocks keep their place): counter reads of a call
-// 1.39 -> 1.03 GB for Riem_Solver3, 1.23 -> 0.75 GB for Riem_Solver_c (tools/lab/riem_lab.hip, opt & 4).
+// 1.39 -> 1.03 GB for Riem_Solver3, 1.23 -> 0.75 GB for Riem_Solver_c (tools/lab/riem_lab.hip).
 FV3_HD void xcd_block(int &bx, int &by, int nbx, int nby) {
   const int flat = by * nbx + bx, chunk = (nbx * nby) >> 3;
   if (flat < chunk * 8) {
@@ -286,7 +286,6 @@ struct EdgeProfileLds {
   Grid g;
   int km;
   EdgeCoef ec;
-  const double *rbet;     // device, km: 1 / ec.bet correctly rounded
   const double *q1, *q2;
   double *q1e, *q2e;
   int n2d;
@@ -294,24 +293,21 @@ struct EdgeProfileLds {
   double *q1e_b, *q2e_b;
   int n2d_b;
   // The rows' coefficients as the host tabulates them (edge_rows() below: 6 x 128 doubles -- bet, 1 / bet, S, G, gk, the factor 3 of the
-  // interior rows -- with the first, the bottom and the padded rows already in place).  tab = NULL: the wavefront builds them itself
-  // with a dozen selects of doubles per row (a select of two doubles is 21 cycles of the SIMD, tools/lab/op_lab.hip: that set-up and
-  // the three selects per row of the right-hand sides were half of the wavefront's instructions).  opt & 1: the two fields of a pair
-  // run their rounds side by side (two independent chains: 5.15 instead of 6.3 cycles an operation).  opt & 2: the blocks of an XCD
-  // are neighbours.  What the kernel waits for is memory, though (tools/lab/edge_lab.hip, C384 L127: 0.465 ms as round 5 left it and
-  // with the table alone; 0.407 with the XCD ranges; 0.356 with three workgroups per CU as well -- tile_waves below; four spill)
-  const double *tab = nullptr;
-  int opt = 3;
+  // interior rows -- with the first, the bottom and the padded rows already in place).  A wavefront that built them itself needed a
+  // dozen selects of doubles per row (a select of two doubles is 21 cycles of the SIMD, tools/lab/op_lab.hip: that set-up and the
+  // three selects per row of the right-hand sides were half of the wavefront's instructions).  The two fields of a pair run their
+  // rounds side by side (two independent chains: 5.15 instead of 6.3 cycles an operation), and the blocks of an XCD are neighbours.
+  // What the kernel waits for is memory, though (tools/lab/edge_lab.hip, C384 L127: 0.465 ms as round 5 left it and with the table
+  // alone; 0.407 with the XCD ranges; 0.356 with three workgroups per CU as well -- tile_waves below; four spill)
+  const double *tab;
   static constexpr int kTabRows = 16 * kFL, kTabDoubles = 6 * kTabRows;
   FV3_HD int nblk_a() const { return (n2d + kFC - 1) / kFC; }
   FV3_HD int nblocks() const { return nblk_a() + (n2d_b + kFC - 1) / kFC; }
   static constexpr int kIt = kFC * 128 / kNT;
   FV3_D void operator()(int bx, int, int, int tid, double *lds) const {
     double *B0 = lds, *B1 = lds + kFBuf;
-    if (opt & 2) {   // neighbouring blocks share 128-byte lines: one contiguous range of blocks per XCD (xcd_block above)
-      int by0 = 0;
-      xcd_block(bx, by0, nblocks(), 1);
-    }
+    int by0 = 0;   // neighbouring blocks share 128-byte lines: one contiguous range of blocks per XCD (xcd_block above)
+    xcd_block(bx, by0, nblocks(), 1);
     const bool second = bx >= nblk_a();
     const int blk = second ? bx - nblk_a() : bx;
     const ix_t ls = (ix_t)(second ? n2d_b : n2d);
@@ -340,84 +336,7 @@ struct EdgeProfileLds {
       }
     }
     FV3_SYNC();
-#ifndef FV3_LAB_EDGE_OLD_PATH
-    {   // (the library always hands the table over; the wavefront-built rows stay for the A / B of tools/lab/edge_lab.hip: compiled into
-        // the same kernel they cost the table path 20 registers and nine spills under the three-wavefront budget)
-      FV3_WAVE_FOR(wv) rows_from_table(wv * 4, B0, B1);
-    }
-#else
-    if (tab) {
-      FV3_WAVE_FOR(wv) rows_from_table(wv * 4, B0, B1);
-    } else {
-    const double xt2 = ec.gk_bot * (ec.gk_bot + 0.5) - ec.a_bot * ec.gam[km - 1];
-    const double r_top = 1. / ec.bet_top, r_bot = 1. / xt2;
-    FV3_WAVE_FOR(wv) {
-      const int c0 = wv * 4;
-      // the coefficients of the lane's rows (the same for every column)
-      vd bet[kFL], rb[kFL], S[kFL], G[kFL], gkv[kFL];
-      vb first[kFL], bot[kFL], mid[kFL];
-      for (int q = 0; q < kFL; q++) {
-        first[q] = vlevel_eq(q, 0);
-        bot[q] = vlevel_eq(q, km);
-        mid[q] = vlevel_lt(q, km) && !first[q];
-        const vd bt = vrow_ld(ec.bet, q, km), rbt = vrow_ld(rbet, q, km);
-        gkv[q] = vrow_ld(ec.gk, q, km);
-        bet[q] = vsel(first[q], vd(ec.bet_top), vsel(bot[q], vd(xt2), vsel(mid[q], bt, vd(1.0))));
-        rb[q] = vsel(first[q], vd(r_top), vsel(bot[q], vd(r_bot), vsel(mid[q], rbt, vd(1.0))));
-        S[q] = vsel(mid[q], vd(1.0), vsel(bot[q], vd(ec.a_bot), vd(0.0)));
-        G[q] = vsel(vlevel_lt(q, km), vrow_ld(ec.gam, q, km), vd(0.0));
-      }
-      vd x1[kFL], x2[kFL];
-      for (int f = 0; f < 2; f++) {
-        const double *B = f ? B1 : B0;
-        vd a[kFL], R[kFL], y[kFL];
-        vd *x = f ? x2 : x1;
-        for (int q = 0; q < kFL; q++) a[q] = vlds_ld(B, c0, q);
-        const vd a_up1 = row_shr<1>(a[kFL - 1], 0.0), a_up2 = row_shr<1>(a[kFL - 2], 0.0), a_dn = row_shl<1>(a[0], 0.0);
-        for (int q = 0; q < kFL; q++) {
-          const vd am1 = q > 0 ? a[q - 1] : a_up1, am2 = q > 1 ? a[q - 2] : (q == 1 ? a_up1 : a_up2);
-          const vd ap1 = q < kFL - 1 ? a[q + 1] : a_dn;
-          const vd r_first = ec.xt1_top * a[q] + ap1;                   // :1631
-          const vd r_mid = 3. * (am1 + gkv[q] * a[q]);                   // :1636
-          const vd r_bot_ = ec.xt1_bot * am1 + am2;                      // :1648 (q(km), q(km-1))
-          R[q] = vsel(first[q], r_first, vsel(bot[q], r_bot_, vsel(mid[q], r_mid, vd(0.0))));
-        }
-        {
-          vd yin(0.0);
-          for (int rnd = 0; rnd < 16; rnd++) {
-            vd v = yin;
-            for (int q = 0; q < kFL; q++) {
-              v = vdiv_r(R[q] - S[q] * v, bet[q], rb[q]);
-              y[q] = v;
-            }
-            const vd ynew = row_shr<1>(v, 0.0);
-            const bool moved = vany_ne(ynew, yin);
-            yin = ynew;
-            if (!moved) break;
-          }
-        }
-        {
-          vd xin(0.0);
-          for (int rnd = 0; rnd < 16; rnd++) {
-            vd xn = xin;
-            for (int q = kFL - 1; q >= 0; q--) {
-              xn = y[q] - G[q] * xn;
-              x[q] = xn;
-            }
-            const vd xnew = row_shl<1>(xn, 0.0);
-            const bool moved = vany_ne(xnew, xin);
-            xin = xnew;
-            if (!moved) break;
-          }
-        }
-      }
-      for (int q = 0; q < kFL; q++) {       // the wavefront's own columns: no other wavefront reads them
-        vlds_st(B0, c0, q, x1[q]);
-        vlds_st(B1, c0, q, x2[q]);
-      }
-    }
-    }
-#endif
+    FV3_WAVE_FOR(wv) rows_from_table(wv * 4, B0, B1);
     FV3_SYNC();
     for (int idx = tid; idx < kFC * 128; idx += kNT) {
       const int col = idx & (kFC - 1), k = idx >> 4;
@@ -466,76 +385,42 @@ struct EdgeProfileLds {
       rhs(B1, c0, gkv, c3, R2);
     }
     vd y1[kFL], y2[kFL];
-#ifdef FV3_LAB_EDGE_SIDE
-    if (FV3_LAB_EDGE_SIDE) {
-#else
-    if (opt & 1) {
-#endif
-      vd in1(0.0), in2(0.0);
-      for (int rnd = 0; rnd < 16; rnd++) {
-        vd v1 = in1, v2 = in2;
+    vd in1(0.0), in2(0.0);
+    for (int rnd = 0; rnd < 16; rnd++) {
+      vd v1 = in1, v2 = in2;
 #ifndef FV3_HOST_EMU
 #pragma unroll
 #endif
-        for (int q = 0; q < kFL; q++) {
-          v1 = vdiv_r(R1[q] - S[q] * v1, bet[q], rb[q]);
-          v2 = vdiv_r(R2[q] - S[q] * v2, bet[q], rb[q]);
-          y1[q] = v1;
-          y2[q] = v2;
-        }
-        const vd n1 = row_shr<1>(v1, 0.0), n2 = row_shr<1>(v2, 0.0);
-        const bool moved = vany_ne(n1, in1) || vany_ne(n2, in2);     // a round more than a field needs leaves it as it is
-        in1 = n1;
-        in2 = n2;
-        if (!moved) break;
+      for (int q = 0; q < kFL; q++) {
+        v1 = vdiv_r(R1[q] - S[q] * v1, bet[q], rb[q]);
+        v2 = vdiv_r(R2[q] - S[q] * v2, bet[q], rb[q]);
+        y1[q] = v1;
+        y2[q] = v2;
       }
-      in1 = vd(0.0);
-      in2 = vd(0.0);
-      for (int rnd = 0; rnd < 16; rnd++) {
-        vd v1 = in1, v2 = in2;
+      const vd n1 = row_shr<1>(v1, 0.0), n2 = row_shr<1>(v2, 0.0);
+      const bool moved = vany_ne(n1, in1) || vany_ne(n2, in2);     // a round more than a field needs leaves it as it is
+      in1 = n1;
+      in2 = n2;
+      if (!moved) break;
+    }
+    in1 = vd(0.0);
+    in2 = vd(0.0);
+    for (int rnd = 0; rnd < 16; rnd++) {
+      vd v1 = in1, v2 = in2;
 #ifndef FV3_HOST_EMU
 #pragma unroll
 #endif
-        for (int q = kFL - 1; q >= 0; q--) {
-          v1 = y1[q] - G[q] * v1;
-          v2 = y2[q] - G[q] * v2;
-          R1[q] = v1;
-          R2[q] = v2;
-        }
-        const vd n1 = row_shl<1>(v1, 0.0), n2 = row_shl<1>(v2, 0.0);
-        const bool moved = vany_ne(n1, in1) || vany_ne(n2, in2);
-        in1 = n1;
-        in2 = n2;
-        if (!moved) break;
+      for (int q = kFL - 1; q >= 0; q--) {
+        v1 = y1[q] - G[q] * v1;
+        v2 = y2[q] - G[q] * v2;
+        R1[q] = v1;
+        R2[q] = v2;
       }
-    } else {
-      for (int f = 0; f < 2; f++) {
-        vd *R = f ? R2 : R1, *y = f ? y2 : y1;
-        vd in(0.0);
-        for (int rnd = 0; rnd < 16; rnd++) {
-          vd v = in;
-          for (int q = 0; q < kFL; q++) {
-            v = vdiv_r(R[q] - S[q] * v, bet[q], rb[q]);
-            y[q] = v;
-          }
-          const vd nw = row_shr<1>(v, 0.0);
-          const bool moved = vany_ne(nw, in);
-          in = nw;
-          if (!moved) break;
-        }
-        in = vd(0.0);
-        for (int rnd = 0; rnd < 16; rnd++) {
-          vd v = in;
-          for (int q = kFL - 1; q >= 0; q--) {
-            v = y[q] - G[q] * v;
-            R[q] = v;
-          }
-          const vd nw = row_shl<1>(v, 0.0);
-          const bool moved = vany_ne(nw, in);
-          in = nw;
-          if (!moved) break;
-        }
-      }
+      const vd n1 = row_shl<1>(v1, 0.0), n2 = row_shl<1>(v2, 0.0);
+      const bool moved = vany_ne(n1, in1) || vany_ne(n2, in2);
+      in1 = n1;
+      in2 = n2;
+      if (!moved) break;
     }
     for (int q = 0; q < kFL; q++) {       // the wavefront's own columns: no other wavefront reads them
       vlds_st(B0, c0, q, R1[q]);
@@ -594,9 +479,9 @@ struct RiemFast {
   // MOIST: q_con (use_cond: the condensates leave the hydrostatic pressure of pm2, nh_core.F90:113-131, :145-154 / nh_utils.F90:383-396,
   // :413-438) and cappa (moist_kappa: gm2, cp2 per cell; on the C grid only together with q_con), A x km or null
   const double *qcon = nullptr, *cappa = nullptr;
-  int probe = 0;   // timing probe (tools/riem_time.py, FV3_MI355X_RIEM_PROBE): 1 one round per sum, 2 no w pass, 4 one round of the pp system -- WRONG results
-  int opt = 7;     // A / B switches of tools/lab/riem_lab.hip (all on in the library): 1 the pass wavefront chosen by SIMD, 2 the sweep in
-                   // alternating register sets, 4 XCD-contiguous column blocks
+  int probe = 0;   // always 0 in the library (tools/lab timing probe: 1 one round per sum, 2 no w pass, 4 one round of the pp system -- WRONG results)
+  int opt = 7;     // always 7 in the library: 1 the pass wavefront chosen by SIMD, 2 the sweep in alternating register sets, 4 XCD-contiguous
+                   // column blocks.  probe, opt and w_column stay although nothing sets them: the kernels without them spill more
   long long *trace = nullptr;   // tools/lab (-DFV3_LAB_TRACE): clock64() of every wavefront at the barriers of block trace_blk
   int trace_blk = -1;
   // LDS: the four transposition buffers + the wavefronts' hardware ids (pass_wave)

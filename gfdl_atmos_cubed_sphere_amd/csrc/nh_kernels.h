@@ -13,8 +13,8 @@
 //
 // Column kernels: one thread per (i,j) column, consecutive threads = consecutive i (coalesced
 // 512-B rows per wavefront at every level), k sequential.  The tridiagonal sweeps keep their
-// O(km) intermediates in context-owned scratch slabs laid out like the fields (i fastest), so every
-// scratch access is coalesced too.  Branches: use_cond = moist_kappa = .false., fast_tau_w_sec = 0,
+// O(km) intermediates in context-owned scratch slabs in per-wavefront blocks (remap_kernels.h scr_col),
+// so every scratch access is coalesced too.  Branches: use_cond = moist_kappa = .false., fast_tau_w_sec = 0,
 // d2bg_zq = 0.
 #pragma once
 
@@ -36,9 +36,9 @@ struct NhConsts {
 
 #define FV3_COL_FOR(c, ncol) for (int c = bx * 256 + tid; c < (bx + 1) * 256 && c < (ncol); c += kNT)
 // The same with a POOL of P workgroups (P > 0: the launch has P workgroups, each takes the column blocks bx, bx + P, ...; cs is
-// the column slot of the scratch slabs: a workgroup reuses its own 256 slots for every block it takes, so the slabs of a launch
-// are P x 256 columns that stay in L2 / Infinity Cache instead of one pass through HBM per sweep of the solver).  P = 0: one
-// workgroup per column block, cs = c.
+// the column slot of the scratch slabs).  The library always launches P = 0: one workgroup per column block, cs = c.  The pooled
+// launches (measured slower) are retired; RiemSolver3 keeps this loop because its straight form takes 173 - 174 VGPRs for 165 - 167,
+// two wavefronts per SIMD for three.
 #define FV3_COL_FOR_POOL(c, cs, ncol, P)                                            \
   for (int bb_ = bx; bb_ < ((ncol) + 255) / 256; bb_ += ((P) > 0 ? (P) : 0x40000000)) \
     for (int c = bb_ * 256 + tid, cs = ((P) > 0 ? bx : bb_) * 256 + tid; c < (bb_ + 1) * 256 && c < (ncol); c += kNT, cs += kNT)
@@ -422,12 +422,10 @@ struct RiemSolverC {
   double *gz, *pef;
   double *s0, *s1, *s2, *s3;  // scratch slabs, A x (km+1)
   const double *q_con, *cappa;  // A x km or null (use_cond / moist_kappa)
-  int scr_blocked;              // scratch slabs in per-wavefront blocks (remap_kernels.h scr_col)
-  int pool;                     // workgroups of a pooled launch (FV3_COL_FOR_POOL; needs scr_blocked), 0 = one per column block
   FV3_HD void operator()(int bx, int, int, int tid, double *) const {
     const int w = g.nx + 2, ncol = w * (g.ny + 2);
     const size_t nA = g.nA();
-    FV3_COL_FOR_POOL(c, cs, ncol, pool) {
+    FV3_COL_FOR(c, ncol) {
       const int i = g.is - 1 + c % w, j = g.js - 1 + c / w;
       const int o = g.iA(i, j);
       ColIn in{delp + o, pt + o, w3 + o, gz + o, 1.};
@@ -438,10 +436,9 @@ struct RiemSolverC {
       // pef = pe2 + pem (:461-465); gz = hs - sum dz2*grav (:468-476), formed inside the solver's last two sweeps
       double pem = cn.ptop;
       double zb = hs[o];
-      const size_t so = scr_blocked ? (size_t)(cs >> 6) * 64 * (km + 1) + (cs & 63) : (size_t)o;
-      const size_t ss = scr_blocked ? 64 : nA;
+      const size_t so = (size_t)(c >> 6) * 64 * (km + 1) + (c & 63);  // per-wavefront blocks (remap_kernels.h scr_col)
       sim_column<MOIST>(
-          km, nA, ss, in, dt, cn, true, true, ws[o], s0 + so, s1 + so, s2 + so, s3 + so,
+          km, nA, 64, in, dt, cn, true, true, ws[o], s0 + so, s1 + so, s2 + so, s3 + so,
           [&](int k, double pe2) {
             if (k == 1) {
               pef[o] = cn.ptop;
@@ -471,8 +468,8 @@ struct RiemSolver3 {
   int use_logp, last_call, fp_out;
   double *s0, *s1, *s2, *s3;
   const double *q_con, *cappa;  // A x km or null (use_cond / moist_kappa, nh_core.F90:96-166)
-  int scr_blocked;
-  int pool;
+  int scr_blocked;              // always 1: scratch slabs in per-wavefront blocks (remap_kernels.h scr_col)
+  int pool;                     // always 0: one workgroup per column block (FV3_COL_FOR_POOL)
   FV3_HD void operator()(int bx, int, int, int tid, double *) const {
     const int ncol = g.nx * g.ny;
     const size_t nA = g.nA(), nCC = g.nCC();

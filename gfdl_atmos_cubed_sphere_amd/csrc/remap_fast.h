@@ -195,12 +195,10 @@ struct RemapFastCoreT {
   using Lay = RLay<L>;
   static constexpr int RL = Lay::RL, kRP = Lay::RP;   // rows of a column the lanes hold, pitch of a column
   int km;
-  int probe = 0;   // timing probe (FV3_MI355X_REMAP_PROBE, tools/remap_time.py; WRONG results): 1 no spline, 2 no constraints, 4 no
-                   // subgrid limiters, 8 no mapping loop
   // tools/lab (-DFV3_LAB_TRACE): clock64() of every wavefront at the phase boundaries of one block, in the order they are passed
+#ifdef FV3_LAB_TRACE
   long long *trace = nullptr;
   mutable int tn = 0;
-#ifdef FV3_LAB_TRACE
   FV3_D void mark(int tid) const { if (trace && (tid & 63) == 0) trace[(tid >> 6) * 128 + (tn < 127 ? tn : 127)] = clock64(); tn++; }
 #else
   FV3_D void mark(int) const {}
@@ -385,9 +383,8 @@ struct RemapFastCoreT {
       if (k > km) continue;
       const RColC a1 = colc(A1, col), q = colc(Q, col), t2 = colc(C2, col);
       double a2v = q[k], a3v = q[k + 1], a4v = 0.;
-      if (!(probe & 4))
-        cs_cell(pc, k, a2v, a3v, k - 2 >= 1 ? a1[k - 2] : 0., k - 1 >= 1 ? a1[k - 1] : 0., a1[k], k + 1 <= km ? a1[k + 1] : 0.,
-                k + 2 <= km ? a1[k + 2] : 0., a4v);
+      cs_cell(pc, k, a2v, a3v, k - 2 >= 1 ? a1[k - 2] : 0., k - 1 >= 1 ? a1[k - 1] : 0., a1[k], k + 1 <= km ? a1[k + 1] : 0.,
+              k + 2 <= km ? a1[k + 2] : 0., a4v);
       r2[it] = a2v; r3v[it] = a3v;
       form[it] = a4_form_of(a4v, a1[k], a2v, a3v);
       pt2[it] = t2[k]; pb2[it] = t2[k + 1];
@@ -405,7 +402,7 @@ struct RemapFastCoreT {
     for (int it = 0; it < kIt; it++) {
       const int idx = tid + it * kNT, col = idx / RL, k = idx % RL + 1;
       if (k > km) continue;
-      if (!(probe & 8)) r2[it] = map_target(colc(C1, col), colc(A1, col), colc(Q, col), colc(C2, col), km, Lay::RC, tracer_form, k, pt2[it], pb2[it]);
+      r2[it] = map_target(colc(C1, col), colc(A1, col), colc(Q, col), colc(C2, col), km, Lay::RC, tracer_form, k, pt2[it], pb2[it]);
     }
     FV3_SYNC_LDS();
     for (int it = 0; it < kIt; it++) {
@@ -425,10 +422,10 @@ struct RemapFastCoreT {
                          double qmin, bool tracer_form, int tid, Pre &&pre) const {
     const int ak = kord < 0 ? -kord : kord;
     mark(tid);   // field start
-    if (!(probe & 1)) { FV3_WAVE_FOR(wv) { spline(C1, A1, Q, QS, iv, wv); } }
+    FV3_WAVE_FOR(wv) { spline(C1, A1, Q, QS, iv, wv); }
     mark(tid);   // spline done
     FV3_SYNC_LDS();
-    if (!(probe & 2)) constrain(A1, Q, iv, ak, tid);
+    constrain(A1, Q, iv, ak, tid);
     FV3_SYNC_LDS();
     mark(tid);   // constrained
     pre();
@@ -458,10 +455,10 @@ struct RemapFastScalars {
   const int *kord_tr;   // device, nq
   const double *pe, *ws;
   double *ps, *delp, *pkz, *pk, *delz, *pt, *peln, *w, *q, *omga;
-  int probe = 0;
-  int opt = 1;     // A / B switch of tools/lab/remap_lab.hip (on in the library): 1 XCD-contiguous column blocks
-  long long *trace = nullptr;   // tools/lab (-DFV3_LAB_TRACE): RemapFastCoreT::mark of block trace_blk
+#ifdef FV3_LAB_TRACE
+  long long *trace = nullptr;   // tools/lab: RemapFastCoreT::mark of block trace_blk
   int trace_blk = -1;
+#endif
 
   FV3_HD int nblocks_x() const { return (g.nx + kFC - 1) / kFC; }
 
@@ -470,8 +467,12 @@ struct RemapFastScalars {
     using Lay = RLay<L>;
     constexpr int kIt = Core::kIt, RL = Core::RL, kRP = Lay::RP, kRBuf = Lay::RBuf;
     double *C1 = lds, *C2 = lds + kRBuf, *A1 = lds + 2 * kRBuf, *Q = lds + 3 * kRBuf, *QS = C1 + Lay::RQS;   // QS[column * kRP]
-    if (opt & 1) xcd_block(bx, by, nblocks_x(), g.ny);   // neighbouring column blocks share 128-byte lines: one L2 for both (nh_fast.h)
-    const Core core{km, probe, by * nblocks_x() + bx == trace_blk ? trace : nullptr};
+    xcd_block(bx, by, nblocks_x(), g.ny);   // neighbouring column blocks share 128-byte lines: one L2 for both (nh_fast.h)
+#ifdef FV3_LAB_TRACE
+    const Core core{km, by * nblocks_x() + bx == trace_blk ? trace : nullptr};
+#else
+    const Core core{km};
+#endif
     core.mark(tid);   // block start
     const int i0 = g.is + bx * kFC, j = g.js + by;
     const int ncol = (g.nx - bx * kFC < kFC) ? g.nx - bx * kFC : kFC;
@@ -792,8 +793,6 @@ struct RemapFastWind {
   int kord_mt;
   const double *ak, *bk, *pe;
   double *f;
-  int probe = 0;
-  int opt = 1;
 
   FV3_HD int ncols_row() const { return WHICH == 0 ? g.nx : g.nx + 1; }
   FV3_HD int nrows() const { return WHICH == 0 ? g.ny + 1 : g.ny; }
@@ -803,10 +802,10 @@ struct RemapFastWind {
     using Core = RemapFastCoreT<L>;
     using Lay = RLay<L>;
     constexpr int kIt = Core::kIt, kRBuf = Lay::RBuf;
-    const Core core{km, probe};
+    const Core core{km};
     double *C1 = lds, *C2 = lds + kRBuf, *A1 = lds + 2 * kRBuf, *Q = lds + 3 * kRBuf;
     double *AK = lds + Lay::TabAk, *BK = lds + Lay::TabBk;
-    if (opt & 1) xcd_block(bx, by, nblocks_x(), nrows());
+    xcd_block(bx, by, nblocks_x(), nrows());
     const int i0 = g.is + bx * kFC, j = g.js + by;
     const int ncol = (ncols_row() - bx * kFC < kFC) ? ncols_row() - bx * kFC : kFC;
     const ix_t fs = WHICH == 0 ? g.nU() : g.nV();

@@ -892,7 +892,7 @@ struct RemapPar {
   double cv_vap, c_liq, c_ice;
   double *q_con, *cappa;  // A x km, written where the reference writes them (fv_mapz.F90:212-219, :463-478)
   int fill;               // flagstruct%fill: fillz on the remapped tracers
-  int scr_blocked;        // layout of the scratch slabs (scr_col)
+  int scr_blocked;        // layout of the scratch slabs (scr_col); always 1 in the library
   // flagstruct%remap_te (fv_mapz.F90:232-286, :348-360, :576-619, :655-663; fv3_set_remap_te): total energy is remapped in the
   // place of T_v / theta_v.  hs: A; te: A x km work array (the reference's te argument); u_old: U x km copy of u before the remap
   int remap_te = 0;

@@ -58,7 +58,8 @@ struct MarchDims {
   int nstrips, nsegs, tj;
   const int *klist;  // level of the n-th marching slab (device), or null = identity
   int nk;            // number of level slots of the launch (set by nwaves)
-  int k_fast;        // 1: consecutive wavefronts = consecutive levels of the same (strip, segment)
+  int k_fast;        // always 0 (1: consecutive wavefronts = consecutive levels of the same (strip, segment), measured twice, slower; the
+                     // switch is retired, the field and its arm stay: without them 14 marching kernels spill 1 - 6 more SGPRs)
   // sub-box of the (strip, segment) grid this launch covers (default: all) -- lets a caller run the strips /
   // segments that do not touch the halo while the halo exchange is still in flight, and the frame afterwards
   int s0, ns, g0, ng;
@@ -131,16 +132,12 @@ struct MarchDims {
     }
   }
 };
-inline int march_k_fast() {
-  static const int v = env_int("FV3_MI355X_K_FAST", 0);  // measured: no gain on MI355X (metric rows are served by L2 / Infinity Cache either way)
-  return v;
-}
 inline MarchDims make_march_dims(const Grid &g, int tj) {
   MarchDims d;
   d.tj = tj;
   d.klist = nullptr;
   d.nk = 0;
-  d.k_fast = march_k_fast();
+  d.k_fast = 0;
   d.nstrips = num_strips(g);
   d.nsegs = (g.ny + tj - 1) / tj;
   d.alt_nk = d.alt_ng = d.alt_tj = 0;

@@ -13,14 +13,6 @@ TOKEN = re.compile(r"FV3_MI355X_[A-Z0-9_]+")
 EXEMPT = {
     "FV3_MI355X_DEBUG_SEGMENTS": "a diagnostic print on stderr, not a path",
     "FV3_MI355X_FACE_GROUP": "Python host: the tests turn the face group off through cubed_dyn's argument, not the environment",
-    # fields of kernel functors whose removal changes device code of kernels the defaults run; they stay until that change has
-    # passed its register and timing gates
-    "FV3_MI355X_RIEM_PROBE": "timing probe inside the LDS Riemann solvers",
-    "FV3_MI355X_REMAP_PROBE": "timing probe inside the LDS remap",
-    "FV3_MI355X_RIEM_SCR": "scratch layout of the slab Riemann solvers, a field of their functors",
-    "FV3_MI355X_REMAP_SCR": "scratch layout of the slab remap, a field of its functors",
-    "FV3_MI355X_COL_POOL": "pooled launches of the slab Riemann solvers, a field of their functors",
-    "FV3_MI355X_K_FAST": "wavefront order of the marching kernels, a field of MarchDims",
 }
 
 

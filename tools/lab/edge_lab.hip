@@ -1,10 +1,6 @@
 // edge_lab.hip -- edge_profile with the levels across the lanes (csrc/nh_fast.h EdgeProfileLds) on a C384 L127 tile, outside the library:
-// the wavefront-built row coefficients against the host's table, the two fields of a pair one after the other against side by side;
-// timed and compared bit for bit.  tools/lab/build.sh edge_lab; run on the GPU box.
+// the shipped kernel timed (-DLAB_EDGE_WAVES=W: with W workgroups per CU).  tools/lab/build.sh edge_lab; run on the GPU box.
 //   edge_lab [nx] [km] [reps]
-#ifndef FV3_LAB_EDGE_TABLE_ONLY
-#define FV3_LAB_EDGE_OLD_PATH 1   // the rows built by the wavefront (round 5), for the comparison
-#endif
 #include "lab_common.h"
 
 #include "../../gfdl_atmos_cubed_sphere_amd/csrc/fv3_launch.h"
@@ -70,19 +66,8 @@ int main(int argc, char **argv) {
   std::printf("edge_lab %d x %d x %d\n", nx, nx, km);
   const double bytes = (double)(nCX + nCY) * (2. * km + 2. * (km + 1)) * 8.;
   auto none = [] {};
-  auto zero = [&] { cxa.zero(); xfa.zero(); cya.zero(); yfa.zero(); };
-  auto grab = [&] {
-    HC(hipDeviceSynchronize());
-    std::vector<std::vector<double>> o{cxa.get(), xfa.get(), cya.get(), yfa.get()};
-    return o;
-  };
-  auto same = [&](const char *what, const std::vector<std::vector<double>> &a, const std::vector<std::vector<double>> &b) {
-    size_t n = 0;
-    for (size_t i = 0; i < a.size(); i++) n += lab::count_diff(a[i], b[i]);
-    std::printf("  %-40s %s (%zu words differ)\n", what, n ? "DIFFERENT" : "bit-identical", n);
-  };
-  auto run = [&](const double *t, int opt) {
-    EdgeProfileLds kf{g, km, ec, cod.d + 3 * km, crx.d, xfx.d, cxa.d, xfa.d, (int)nCX, cry.d, yfx.d, cya.d, yfa.d, (int)nCY, t, opt};
+  auto run = [&] {
+    EdgeProfileLds kf{g, km, ec, crx.d, xfx.d, cxa.d, xfa.d, (int)nCX, cry.d, yfx.d, cya.d, yfa.d, (int)nCY, tab.d};
 #ifdef LAB_EDGE_WAVES
     int rc = launch_2w(Dim3{(unsigned)kf.nblocks(), 1, 1}, 2 * kFBuf, 0, kf);
 #else
@@ -90,24 +75,6 @@ int main(int argc, char **argv) {
 #endif
     if (rc) { std::fprintf(stderr, "launch failed %d\n", rc); std::exit(3); }
   };
-  zero();
-#ifdef FV3_LAB_EDGE_TABLE_ONLY
-  run(tab.d, 0);
-  const auto ref = grab();
-#else
-  run(nullptr, 0);
-  const auto ref = grab();
-  lab::time_it("edge_profile, rows built by the wavefront (round 5)", reps, none, [&] { run(nullptr, 0); }, bytes);
-#endif
-  for (int opt = 0; opt < 4; opt++) {
-    zero();
-    run(tab.d, opt);
-    const auto o = grab();
-    char label[128];
-    std::snprintf(label, sizeof label, "edge_profile, rows from the host's table, opt %d", opt);
-    lab::time_it(label, reps, none, [&] { run(tab.d, opt); }, bytes);
-    same(label, ref, o);
-  }
-  // km not a multiple of 8 minus 1, and a small one: the bottom row sits elsewhere in its lane
+  lab::time_it("edge_profile", reps, none, run, bytes);
   return 0;
 }

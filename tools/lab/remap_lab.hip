@@ -1,5 +1,6 @@
 // remap_lab.hip -- Lagrangian_to_Eulerian's levels-across-the-lanes kernels (csrc/remap_fast.h) on a synthetic C384 L127 tile with 4 tracers,
-// outside the library: variants timed against each other and compared bit for bit.  tools/lab/build.sh remap_lab; run on the GPU box.
+// outside the library: the shipped kernels timed; with -DFV3_LAB_TRACE also the phase timeline of a block.
+// tools/lab/build.sh remap_lab [-DFV3_LAB_TRACE]; run on the GPU box.
 //   remap_lab [nx] [km] [reps] [nq]
 #include "lab_common.h"
 
@@ -104,27 +105,12 @@ static void reset(State &s) {
   cp(s.peln, s.peln0); cp(s.pk, s.pk0); cp(s.u, s.u0); cp(s.v, s.v0);
 }
 
-struct Out { std::vector<double> ps, delp, pkz, pk, delz, pt, peln, w, q, omga, u, v; };
-static Out grab(State &s) {
-  HC(hipDeviceSynchronize());
-  return Out{s.ps.get(), s.delp.get(), s.pkz.get(), s.pk.get(), s.delz.get(), s.pt.get(), s.peln.get(), s.w.get(), s.q.get(), s.omga.get(),
-             s.u.get(), s.v.get()};
-}
-static bool same(const char *what, const Out &a, const Out &b) {
-  size_t n = 0;
-  n += lab::count_diff(a.ps, b.ps); n += lab::count_diff(a.delp, b.delp); n += lab::count_diff(a.pkz, b.pkz); n += lab::count_diff(a.pk, b.pk);
-  n += lab::count_diff(a.delz, b.delz); n += lab::count_diff(a.pt, b.pt); n += lab::count_diff(a.peln, b.peln); n += lab::count_diff(a.w, b.w);
-  n += lab::count_diff(a.q, b.q); n += lab::count_diff(a.omga, b.omga); n += lab::count_diff(a.u, b.u); n += lab::count_diff(a.v, b.v);
-  std::printf("  %-44s %s (%zu words differ)\n", what, n ? "DIFFERENT" : "bit-identical", n);
-  return n == 0;
-}
-
 template <int L>
 static RemapFastScalars<false, false, L> make_sc(State &s, int last_step) {
   RemapPar rp = s.rp;
   rp.last_step = last_step;
   return RemapFastScalars<false, false, L>{s.g, s.km, rp, s.ak.d, s.bk.d, s.kord_tr, s.pe.d, s.ws.d, s.ps.d, s.delp.d, s.pkz.d, s.pk.d, s.delz.d,
-                                           s.pt.d, s.peln.d, s.w.d, s.q.d, s.omga.d, 0};
+                                           s.pt.d, s.peln.d, s.w.d, s.q.d, s.omga.d};
 }
 template <class K>
 static void go(const K &k, unsigned gx, unsigned gy, size_t lds_doubles) {
@@ -151,46 +137,12 @@ int main(int argc, char **argv) {
     go(a, (unsigned)a.nblocks_x(), (unsigned)a.nrows(), lds);
     go(b, (unsigned)b.nblocks_x(), (unsigned)b.nrows(), lds);
   };
-  Out ref;
   {
-    auto k0 = sc; auto a0 = wu; auto b0 = wv;
-#ifdef LAB_OPT
-    k0.opt = 0; a0.opt = 0; b0.opt = 0;
-#endif
-    reset(s); all(k0, a0, b0); ref = grab(s);
     double bytes = cells * 8. * (2 * (3 + nq) + 2 + 4 + 5);   // in and out of T_v, w, delz, tracers; u, v; pe, peln, pk in; delp, pkz, pk, peln, ps out
-    lab::time_it("remap scalars (round 5)", reps, rs, [&] { go(k0, gx, (unsigned)nx, lds); });
-    lab::time_it("remap winds u + v (round 5)", reps, rs, [&] { go(a0, (unsigned)a0.nblocks_x(), (unsigned)a0.nrows(), lds); go(b0, (unsigned)b0.nblocks_x(), (unsigned)b0.nrows(), lds); });
-    lab::time_it("remap all three (round 5)", reps, rs, [&] { all(k0, a0, b0); }, bytes);
-    for (int pr : {1, 2, 4, 8, 15}) {
-      auto kp = k0; kp.probe = pr;
-      char lb[96];
-      std::snprintf(lb, sizeof lb, "remap scalars (round 5) probe %d (wrong results)", pr);
-      lab::time_it(lb, reps, rs, [&] { go(kp, gx, (unsigned)nx, lds); });
-    }
+    lab::time_it("remap scalars", reps, rs, [&] { go(sc, gx, (unsigned)nx, lds); });
+    lab::time_it("remap winds u + v", reps, rs, [&] { go(wu, (unsigned)wu.nblocks_x(), (unsigned)wu.nrows(), lds); go(wv, (unsigned)wv.nblocks_x(), (unsigned)wv.nrows(), lds); });
+    lab::time_it("remap all three", reps, rs, [&] { all(sc, wu, wv); }, bytes);
   }
-#ifdef LAB_OPT
-  for (int opt : {LAB_OPT}) {
-    auto k1 = sc; auto a1 = wu; auto b1 = wv;
-    k1.opt = opt; a1.opt = opt; b1.opt = opt;
-    char lb[96];
-    std::snprintf(lb, sizeof lb, "remap scalars opt %d", opt);
-    lab::time_it(lb, reps, rs, [&] { go(k1, gx, (unsigned)nx, lds); });
-    std::snprintf(lb, sizeof lb, "remap winds u + v opt %d", opt);
-    lab::time_it(lb, reps, rs, [&] { go(a1, (unsigned)a1.nblocks_x(), (unsigned)a1.nrows(), lds); go(b1, (unsigned)b1.nblocks_x(), (unsigned)b1.nrows(), lds); });
-    std::snprintf(lb, sizeof lb, "remap all three opt %d", opt);
-    lab::time_it(lb, reps, rs, [&] { all(k1, a1, b1); });
-    reset(s); all(k1, a1, b1); same(lb, ref, grab(s));
-    {
-      auto kl0 = make_sc<L>(s, 1); kl0.opt = 0;
-      auto kl1 = make_sc<L>(s, 1); kl1.opt = opt;
-      reset(s); go(kl0, gx, (unsigned)nx, lds); Out r0 = grab(s);
-      reset(s); go(kl1, gx, (unsigned)nx, lds);
-      std::snprintf(lb, sizeof lb, "remap scalars opt %d, last step", opt);
-      same(lb, r0, grab(s));
-    }
-  }
-#endif
 #ifdef FV3_LAB_TRACE
   {
     long long *tr;

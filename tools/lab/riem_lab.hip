@@ -1,13 +1,11 @@
 // riem_lab.hip -- the Riemann solvers' levels-across-the-lanes kernels (csrc/nh_fast.h) on a synthetic C384 L127 tile, outside the
-// library: variants timed against each other and compared bit for bit.  tools/lab/build.sh riem_lab; run on the GPU box.
+// library: the shipped kernels timed; with -DFV3_LAB_TRACE also the w pass alone, the forward sweep with and without its LDS traffic and
+// per-barrier timelines of a block.  tools/lab/build.sh riem_lab [-DFV3_LAB_TRACE]; run on the GPU box.
 //   riem_lab [nx] [km]
 #include "lab_common.h"
 
 #include "../../gfdl_atmos_cubed_sphere_amd/csrc/fv3_launch.h"
 #include "../../gfdl_atmos_cubed_sphere_amd/csrc/nh_fast.h"
-#ifdef LAB_HAVE_NEW
-#include "../../gfdl_atmos_cubed_sphere_amd/csrc/nh_col.h"
-#endif
 
 using namespace fv3;
 using lab::DevArr;
@@ -68,9 +66,6 @@ static void reset(State &s) {
   HC(hipMemcpyAsync(s.gz.d, s.zh0.d, s.gz.n * 8, hipMemcpyDeviceToDevice, 0));
 }
 
-struct Out3 { std::vector<double> zh, w, delz, ppe, pk3, pe, pk, peln; };
-struct OutC { std::vector<double> gz, pef; };
-
 template <class K>
 static K make3(State &s, double dt, int last_call) {
   return K{s.g, s.km, dt, s.cn, s.zs.d, s.pt.d, s.delp.d, s.ws_cc.d, s.w.d, s.zh.d, s.delz.d, s.ppe.d, s.pk3.d, s.pe.d, s.pk.d, s.peln.d, nullptr,
@@ -85,26 +80,6 @@ static void go(const K &k, size_t lds_doubles) {
   int rc = launch_2w(Dim3{(unsigned)k.nblocks_x(), (unsigned)k.nrows(), 1}, lds_doubles, 0, k);
   if (rc) { std::fprintf(stderr, "launch failed %d\n", rc); std::exit(3); }
 }
-static Out3 grab3(State &s) {
-  HC(hipDeviceSynchronize());
-  return Out3{s.zh.get(), s.w.get(), s.delz.get(), s.ppe.get(), s.pk3.get(), s.pe.get(), s.pk.get(), s.peln.get()};
-}
-static OutC grabc(State &s) {
-  HC(hipDeviceSynchronize());
-  return OutC{s.gz.get(), s.pef.get()};
-}
-static bool same3(const char *what, const Out3 &a, const Out3 &b) {
-  size_t n = 0;
-  n += lab::count_diff(a.zh, b.zh); n += lab::count_diff(a.w, b.w); n += lab::count_diff(a.delz, b.delz); n += lab::count_diff(a.ppe, b.ppe);
-  n += lab::count_diff(a.pk3, b.pk3); n += lab::count_diff(a.pe, b.pe); n += lab::count_diff(a.pk, b.pk); n += lab::count_diff(a.peln, b.peln);
-  std::printf("  %-40s %s (%zu words differ)\n", what, n ? "DIFFERENT" : "bit-identical", n);
-  return n == 0;
-}
-static bool samec(const char *what, const OutC &a, const OutC &b) {
-  size_t n = lab::count_diff(a.gz, b.gz) + lab::count_diff(a.pef, b.pef);
-  std::printf("  %-40s %s (%zu words differ)\n", what, n ? "DIFFERENT" : "bit-identical", n);
-  return n == 0;
-}
 
 void pass_bench(State &s);
 void fwd_bench(int km);
@@ -116,44 +91,12 @@ int main(int argc, char **argv) {
   const double cells = (double)nx * nx * km;
   std::printf("riem_lab %d x %d x %d\n", nx, nx, km);
   auto rs = [&] { reset(s); };
-  // ---- opt = 0: the kernels as round 5 left them: the reference for everything below
-  Out3 ref3, ref3l;
-  OutC refc;
   const size_t lds_n = RiemFast<false, true>::kLdsDoubles;
   {
     auto k = make3<RiemFast<false, true>>(s, 22.5, 0);
-    auto kl = make3<RiemFast<false, true>>(s, 22.5, 1);
     auto kc = makec<RiemFast<true, true>>(s, 11.25);
-    k.opt = kl.opt = kc.opt = 0;
-    reset(s); go(kl, lds_n); HC(hipDeviceSynchronize());   // (pe, pk, peln are written by the last call only: fill them first)
-    reset(s); go(k, lds_n); ref3 = grab3(s);
-    lab::time_it("riem3 RiemFast opt 0 (round 5)", reps, rs, [&] { go(k, lds_n); }, cells * 72);
-    reset(s); go(kl, lds_n); ref3l = grab3(s);
-    reset(s); go(kc, lds_n); refc = grabc(s);
-    lab::time_it("riemC RiemFast opt 0 (round 5)", reps, rs, [&] { go(kc, lds_n); }, cells * 48);
-    for (int pr : {2, 7}) {
-      auto kp = k; kp.probe = pr;
-      auto kcp = kc; kcp.probe = pr;
-      char lb[96];
-      std::snprintf(lb, sizeof lb, "riem3 RiemFast opt 0 probe %d (wrong results)", pr);
-      lab::time_it(lb, reps, rs, [&] { go(kp, lds_n); }, cells * 72);
-      std::snprintf(lb, sizeof lb, "riemC RiemFast opt 0 probe %d (wrong results)", pr);
-      lab::time_it(lb, reps, rs, [&] { go(kcp, lds_n); }, cells * 48);
-    }
-    for (int opt : {1, 2, 4, 7}) {
-      auto ko = k; ko.opt = opt;
-      auto klo = kl; klo.opt = opt;
-      auto kco = kc; kco.opt = opt;
-      char lb[96];
-      std::snprintf(lb, sizeof lb, "riem3 RiemFast opt %d", opt);
-      lab::time_it(lb, reps, rs, [&] { go(ko, lds_n); }, cells * 72);
-      reset(s); go(ko, lds_n); same3(lb, ref3, grab3(s));
-      std::snprintf(lb, sizeof lb, "riem3 RiemFast opt %d, last call", opt);
-      reset(s); go(klo, lds_n); same3(lb, ref3l, grab3(s));
-      std::snprintf(lb, sizeof lb, "riemC RiemFast opt %d", opt);
-      lab::time_it(lb, reps, rs, [&] { go(kco, lds_n); }, cells * 48);
-      reset(s); go(kco, lds_n); samec(lb, refc, grabc(s));
-    }
+    lab::time_it("riem3 RiemFast", reps, rs, [&] { go(k, lds_n); }, cells * 72);
+    lab::time_it("riemC RiemFast", reps, rs, [&] { go(kc, lds_n); }, cells * 48);
   }
 #ifdef FV3_LAB_TRACE
   pass_bench(s);
@@ -183,14 +126,10 @@ int main(int argc, char **argv) {
       }
   }
 #endif
-#ifdef LAB_HAVE_NEW
-  lab_new(s, ref3, ref3l, refc, reps, cells);
-#endif
   return 0;
 }
 
 // ---- the w pass alone: LDS filled with regular coefficients, one workgroup, clock64 around the sweep --------------------------------
-template <int WHICH>
 __global__ void __launch_bounds__(256) pass_only(RiemFast<false, true> k, long long *cyc, double *out) {
   extern __shared__ double fv3_lds[];
   double *B0 = fv3_lds, *B1 = fv3_lds + kFBuf, *B2 = fv3_lds + 2 * kFBuf;
@@ -204,8 +143,7 @@ __global__ void __launch_bounds__(256) pass_only(RiemFast<false, true> k, long l
   const long long t0 = clock64();
   if ((tid >> 6) == 0 && (tid & 63) < kFC) {
     const int col = tid & 63;
-    if (WHICH == 0) k.w_column(B0 + col * kFP, B1 + col * kFP, B2 + col * kFP);
-    else k.w_column2(B0 + col * kFP, B1 + col * kFP, B2 + col * kFP);
+    k.w_column2(B0 + col * kFP, B1 + col * kFP, B2 + col * kFP);
   }
   const long long t1 = clock64();
   if (tid == 0) cyc[blockIdx.x] = t1 - t0;
@@ -218,17 +156,14 @@ void pass_bench(State &s) {
   HC(hipMalloc(&cyc, 8 * 1024));
   HC(hipMalloc(&out, 8 * 256 * 1024));
   auto k = make3<RiemFast<false, true>>(s, 22.5, 0);
-  HC(hipFuncSetAttribute(reinterpret_cast<const void *>(&pass_only<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-  HC(hipFuncSetAttribute(reinterpret_cast<const void *>(&pass_only<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-  for (int which = 0; which < 2; which++)
-    for (int nb : {1, 256}) {
-      if (which) pass_only<1><<<nb, 256, 100 * 1024>>>(k, cyc, out);
-      else pass_only<0><<<nb, 256, 100 * 1024>>>(k, cyc, out);
-      HC(hipDeviceSynchronize());
-      long long c;
-      HC(hipMemcpy(&c, cyc, 8, hipMemcpyDeviceToHost));
-      std::printf("pass alone (%s), %d workgroups: %lld cycles = %.1f per level\n", which ? "w_column2" : "w_column", nb, c, (double)c / s.km);
-    }
+  HC(hipFuncSetAttribute(reinterpret_cast<const void *>(&pass_only), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
+  for (int nb : {1, 256}) {
+    pass_only<<<nb, 256, 100 * 1024>>>(k, cyc, out);
+    HC(hipDeviceSynchronize());
+    long long c;
+    HC(hipMemcpy(&c, cyc, 8, hipMemcpyDeviceToHost));
+    std::printf("pass alone (w_column2), %d workgroups: %lld cycles = %.1f per level\n", nb, c, (double)c / s.km);
+  }
 }
 
 // ---- attribution of the forward sweep's time: MODE 0 as w_column2; 1 no LDS stores; 2 no LDS loads inside the loop; 3 neither ----
