@@ -32,6 +32,7 @@
 #include "phys_update.h"
 #include "held_suarez.h"
 #include "reed_phys.h"
+#include "kessler_phys.h"
 #include "diag_kernels.h"
 #include "remap_kernels.h"
 #include "remap_fast.h"
@@ -173,6 +174,11 @@ struct fv3_ctx {
   int reed_tab_test = -1;
   double *reed_wk = nullptr;
   double *term_k1 = nullptr;
+  // K_warm_rain (kessler_phys.h): table_w and des_w of qs_tables.F90 (fv3_qs_wat_init), 2 x 2621, and the constants they were formed
+  // with; the twelve planes that hold a column's state between cycles, 12 x (is:ie, js:je, npz), a work array under the poison contract
+  double *qs_tab = nullptr;
+  fv3_kessler_consts qs_consts{};
+  double *kessler_wk = nullptr;
   std::vector<double> host_area;   // prt_maxmin: area on the host, and g_sum's global_area
   double global_area = 0.;
   int march_tj_fused = kMarchTj;   // rows per segment of the fused d_sw kernels, transports and momentum (FV3_MI355X_MARCH_TJ_FUSED)
@@ -716,6 +722,8 @@ extern "C" int fv3_destroy(fv3_ctx *c) {
   if (c->reed_tab) rt_free(c->reed_tab);
   work_free(c, &c->reed_wk);
   if (c->term_k1) rt_free(c->term_k1);
+  if (c->qs_tab) rt_free(c->qs_tab);
+  work_free(c, &c->kessler_wk);
   if (c->stream2) rt_stream_destroy(c->stream2);
   if (c->ev_fork) rt_event_destroy(c->ev_fork);
   if (c->ev_join) rt_event_destroy(c->ev_join);
@@ -4958,6 +4966,124 @@ extern "C" int fv3_terminator_advance(fv3_ctx *c, int km, double pdt, int term_f
   grid.y = 1;
   grid.z = 1;
   RT(launch_p(c, "terminator_advance", grid, 0, kf));
+  return 0;
+}
+
+// ---- K_warm_rain, kessler_imp and the qs_wat table (kessler_phys.h) ----------------------------------------------------------------
+static const char *kessler_consts_bad(const fv3_kessler_consts *k) {
+  if (!(k->rdgas > 0.)) return "rdgas";
+  if (!(k->rvgas > 0.)) return "rvgas";
+  if (!(k->cp_air > 0.)) return "cp_air";
+  if (!(k->grav > 0.)) return "grav";
+  if (!(k->kappa > 0.)) return "kappa";
+  return nullptr;
+}
+
+static bool kessler_consts_same(const fv3_kessler_consts *a, const fv3_kessler_consts *b) {
+  return a->rdgas == b->rdgas && a->rvgas == b->rvgas && a->cp_air == b->cp_air && a->cp_vapor == b->cp_vapor && a->hlv == b->hlv &&
+         a->c_liq == b->c_liq && a->grav == b->grav && a->kappa == b->kappa;
+}
+
+extern "C" int fv3_qs_wat_init(fv3_ctx *c, const fv3_kessler_consts *k) {
+  if (!c || !k) return fail("fv3_qs_wat_init: null argument");
+  if (const char *bad = kessler_consts_bad(k)) return fail("fv3_qs_wat_init: %s <= 0", bad);
+  // qs_tables.F90:32-43
+  const double e0 = 610.71, tice = 273.16;
+  const double cp_vap = k->cp_vapor;
+  const double dc_vap = cp_vap - k->c_liq;
+  const double Lv0 = k->hlv - dc_vap * tice;
+  const double del_t = 0.1, tmin = tice - 160.;   // :118, :123
+  std::vector<double> tab(2 * (size_t)kQsLen);
+  double *table_w = tab.data(), *des_w = tab.data() + kQsLen;
+  for (int i = 1; i <= kQsLen; i++) {   // :125-130
+    const double tem = tmin + del_t * (double)(i - 1);
+    table_w[i - 1] = e0 * std::exp((dc_vap * std::log(tem / tice) + Lv0 * (tem - tice) / (tem * tice)) / k->rvgas);
+  }
+  for (int i = 1; i <= kQsLen - 1; i++) des_w[i - 1] = std::fmax(0., table_w[i] - table_w[i - 1]);   // :106-109
+  des_w[kQsLen - 1] = des_w[kQsLen - 2];
+  if (c->qs_tab) {   // a launch that an fv3_group still holds reads the old table: the queues run before it changes
+    if (int rc = grp_flush_all()) return rc;
+    RT(rtf_sync(c->stream));
+  } else {
+    RT(rt_malloc((void **)&c->qs_tab, tab.size() * sizeof(double)));
+  }
+  RT(rtf_h2d(c->qs_tab, tab.data(), tab.size() * sizeof(double), c->stream));
+  RT(rtf_sync(c->stream));
+  c->qs_consts = *k;
+  return 0;
+}
+
+extern "C" int fv3_qs_wat_download(fv3_ctx *c, double *table_w, double *des_w) {
+  if (!c || !table_w || !des_w) return fail("fv3_qs_wat_download: null argument");
+  if (!c->qs_tab) return fail("fv3_qs_wat_download: no table (fv3_qs_wat_init)");
+  RT(rtf_d2h(table_w, c->qs_tab, kQsLen * sizeof(double), c->stream));
+  RT(rtf_d2h(des_w, c->qs_tab + kQsLen, kQsLen * sizeof(double), c->stream));
+  RT(rtf_sync(c->stream));
+  return 0;
+}
+
+extern "C" int fv3_k_warm_rain(fv3_ctx *c, const fv3_kessler_params *p, double *ua, double *va, double *w, double *u_dt, double *v_dt,
+                               double *q, double *pt, double *delp, const double *delz, double *pe, double *peln, double *pk, double *ps,
+                               double *rain) {
+  FV3_ENTRY(c);
+  if (!c || !c->grid_ready) return fail("fv3_k_warm_rain: context has no grid");
+  if (!p || !ua || !va || !u_dt || !v_dt || !q || !pt || !delp || !pe || !peln || !pk || !ps || !rain)
+    return fail("fv3_k_warm_rain: null parameters / field");
+  const bool tr = p->K_sedi_transport != 0, sw = tr && p->do_K_sedi_w != 0, sh = p->do_K_sedi_heat != 0;
+  if (!delz && (!p->hydrostatic || sh)) return fail("fv3_k_warm_rain: null delz with hydrostatic = 0 or do_K_sedi_heat");
+  if (!w && sw) return fail("fv3_k_warm_rain: null w with do_K_sedi_w");
+  const Grid &g = c->g;
+  if (g.npz < 1) return fail("fv3_k_warm_rain: npz = %d < 1", g.npz);
+  if (!(p->pdt > 0.)) return fail("fv3_k_warm_rain: pdt = %g <= 0", p->pdt);
+  if (p->K_cycle < 0) return fail("fv3_k_warm_rain: K_cycle = %d < 0", p->K_cycle);
+  if (const char *bad = kessler_consts_bad(&p->k)) return fail("fv3_k_warm_rain: %s <= 0", bad);
+  if (!c->qs_tab) return fail("fv3_k_warm_rain: no qs_wat table (fv3_qs_wat_init)");
+  if (!kessler_consts_same(&c->qs_consts, &p->k)) return fail("fv3_k_warm_rain: the qs_wat table was uploaded with other constants");
+  const int tri[3] = {p->sphum, p->liq_wat, p->rainwat};
+  for (int n = 0; n < 3; n++)
+    if (tri[n] < 1 || tri[n] > p->nq)
+      return fail("fv3_k_warm_rain: tracer indices sphum = %d, liq_wat = %d, rainwat = %d are not in 1..nq = %d", tri[0], tri[1], tri[2], p->nq);
+  if (tri[0] == tri[1] || tri[0] == tri[2] || tri[1] == tri[2])
+    return fail("fv3_k_warm_rain: tracer indices sphum = %d, liq_wat = %d, rainwat = %d are not distinct", tri[0], tri[1], tri[2]);
+  const int ncyc = p->K_cycle ? p->K_cycle : std::max(1, (int)std::lround(p->pdt / 30.));   // fv_phys.F90:472-474
+  if (ncyc > 1 && !c->kessler_wk) RT(work_alloc(c, "kessler_wk", 0, &c->kessler_wk, 12 * g.nCC() * (size_t)g.npz));
+  // fv_phys.F90:74-85, :470, :2021-2022; qs_tables.F90:79: each scalar a leading sub-expression of the reference's
+  const double tice = 273.16;
+  KesslerScalars s;
+  s.dt = p->pdt;
+  s.sdt = p->pdt / (double)ncyc;
+  s.grav = p->k.grav;
+  s.rgrav = 1. / p->k.grav;
+  s.rdgas = p->k.rdgas;
+  s.rvgas = p->k.rvgas;
+  s.kappa = p->k.kappa;
+  s.rdrg = p->k.rdgas * s.rgrav;
+  s.zvir = p->k.rvgas / p->k.rdgas - 1.;
+  const double cp_vap = p->k.cp_vapor;
+  s.cv_vap = cp_vap - p->k.rvgas;
+  s.cv_air = p->k.cp_air - p->k.rdgas;
+  s.c_liq = p->k.c_liq;
+  s.dc_vap = cp_vap - p->k.c_liq;
+  s.Lv0 = p->k.hlv - s.dc_vap * tice;
+  s.hlv_cv = p->k.hlv / s.cv_air;
+  s.tmin = tice - 160.;
+  s.hg = 0.5 * p->k.grav;
+  s.sdt22 = s.sdt * 2.2;
+  auto go = [&](auto H, auto M, auto T, auto W, auto E) -> int {
+    KWarmRain<decltype(H)::value, decltype(M)::value, decltype(T)::value, decltype(W)::value, decltype(E)::value> kf{
+        g, ncyc, p->sphum - 1, p->liq_wat - 1, p->rainwat - 1, s, c->qs_tab, c->qs_tab + kQsLen, ua, va, w, u_dt, v_dt, q, pt, delp, delz,
+        pe, peln, pk, ps, rain, ncyc > 1 ? c->kessler_wk : nullptr};
+    static_assert(decltype(kf)::CH == 256, "col_grid");
+    return launch_p(c, "k_warm_rain", col_grid(g.nx * g.ny), 0, kf);
+  };
+  auto heat = [&](auto H, auto M, auto T, auto W) -> int { return sh ? go(H, M, T, W, std::true_type{}) : go(H, M, T, W, std::false_type{}); };
+  auto trans = [&](auto H, auto M) -> int {   // do_K_sedi_w is read only inside K_sedi_transport
+    if (!tr) return heat(H, M, std::false_type{}, std::false_type{});
+    return sw ? heat(H, M, std::true_type{}, std::true_type{}) : heat(H, M, std::true_type{}, std::false_type{});
+  };
+  auto mk = [&](auto H) -> int { return p->moist_kappa ? trans(H, std::true_type{}) : trans(H, std::false_type{}); };
+  if (p->hydrostatic) RT(mk(std::true_type{}));
+  else RT(mk(std::false_type{}));
   return 0;
 }
 

@@ -31,6 +31,7 @@ module fv3_mi355x_mod
   public :: fv3_grid_upload_lat, fv3_held_suarez_tend, fv3_held_suarez_params, fv3_age_of_air
   public :: fv3_grid_upload_reed, fv3_reed_sim_phys, fv3_reed_consts, fv3_reed_params, fv3_grid_upload_terminator, fv3_terminator_advance
   public :: fv3_grid_download_reed, fv3_grid_download_terminator
+  public :: fv3_qs_wat_init, fv3_qs_wat_download, fv3_k_warm_rain, fv3_kessler_consts, fv3_kessler_params
 
   type, bind(C) :: fv3_domain
     integer(c_int) :: is, ie, js, je, ng, npx, npy, npz, grid_type
@@ -132,6 +133,19 @@ module fv3_mi355x_mod
     integer(c_int) :: do_reed_cond = 1, reed_cond_only = 0, reed_alt_mxg = 0
     integer(c_int) :: fresh = 0
     type(fv3_reed_consts) :: k
+  end type
+
+  type, bind(C) :: fv3_kessler_consts       ! what K_warm_rain, kessler_imp and qs_tables_mod read of constants_mod and gfdl_mp_mod (c_liq)
+    real(c_double) :: rdgas, rvgas, cp_air, cp_vapor, hlv, c_liq, grav, kappa
+  end type
+
+  type, bind(C) :: fv3_kessler_params       ! K_warm_rain (driver/solo/fv_phys.F90:466-499, :1992-2291): pdt; K_cycle, 0 = max(1,
+    real(c_double) :: pdt                   ! nint(pdt/30.)); the three switches of Kessler_sim_phys_nml; hydrostatic, moist_kappa;
+    integer(c_int) :: K_cycle = 0           ! nq and the 1-based tracer indices sphum, liq_wat, rainwat
+    integer(c_int) :: K_sedi_transport = 0, do_K_sedi_w = 0, do_K_sedi_heat = 0
+    integer(c_int) :: hydrostatic = 0, moist_kappa = 0
+    integer(c_int) :: nq, sphum, liq_wat, rainwat
+    type(fv3_kessler_consts) :: k
   end type
 
   type, bind(C) :: fv3_grid_dwinds    ! what update_dwinds_phys reads of the gridstruct on the sphere (fv_grid_utils.F90:3314-3326):
@@ -782,6 +796,28 @@ module fv3_mi355x_mod
       type(c_ptr), value :: ctx, cl, cl2
       integer(c_int), value :: km, term_fill_negative
       real(c_double), value :: pdt
+    end function
+    ! qs_wat_init (driver/solo/qs_tables.F90:95-132): table_w, des_w formed on the host in the reference's expressions and uploaded;
+    ! once per context, before the first fv3_k_warm_rain, in the place of `call qs_wat_init`
+    integer(c_int) function fv3_qs_wat_init(ctx, k) bind(C, name="fv3_qs_wat_init")
+      import :: c_int, c_ptr, fv3_kessler_consts
+      type(c_ptr), value :: ctx
+      type(fv3_kessler_consts), intent(in) :: k
+    end function
+    ! the two arrays back on the host, for checks: table_w(2621), des_w(2621)
+    integer(c_int) function fv3_qs_wat_download(ctx, table_w, des_w) bind(C, name="fv3_qs_wat_download")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: ctx, table_w, des_w
+    end function
+    ! K_warm_rain with kessler_imp (driver/solo/fv_phys.F90:494-497, :1992-2291), the state in place: ua, va, w, u_dt, v_dt, pt, delp
+    ! (A x npz), q = c_loc(q(isd, jsd, 1, 1)) with p%nq tracers, delz (is:ie, js:je, npz), pe, peln, pk, ps (A), rain (is:ie, js:je).
+    ! w may be c_null_ptr without do_K_sedi_w, delz when hydrostatic without do_K_sedi_heat.  With K_sedi_transport the caller
+    ! goes on with fv3_fv_update_phys (no_tendency false, :499)
+    integer(c_int) function fv3_k_warm_rain(ctx, p, ua, va, w, u_dt, v_dt, q, pt, delp, delz, pe, peln, pk, ps, rain) &
+        bind(C, name="fv3_k_warm_rain")
+      import :: c_int, c_ptr, fv3_kessler_params
+      type(c_ptr), value :: ctx, ua, va, w, u_dt, v_dt, q, pt, delp, delz, pe, peln, pk, ps, rain
+      type(fv3_kessler_params), intent(in) :: p
     end function
     ! interpolate_vertical (tools/fv_diagnostics.F90:4910-4948): a3 (km layers) at the pressure plev [Pa] into a2 (is:ie, js:je).
     ! in_ng = 0: a3 on the compute domain, as the reference's argument; in_ng = ng: a state field with its halo, in the place of the

@@ -315,6 +315,50 @@ class FvDynamics:
         self.atmosphere_step(bdt)
         self.reed_sim_phys(bdt, **reed)
 
+    # -- Kessler warm-rain microphysics -----------------------------------------------------------------------------
+    def k_warm_rain(self, dt: float, K_cycle: int = 0, K_sedi_transport: bool = False, do_K_sedi_w: bool = False, do_K_sedi_heat: bool = False,
+                    consts: dict | None = None):
+        """the do_K_warm_rain path of fv_phys (driver/solo/fv_phys.F90:292-313, :466-499, :675-687) on the resident state, a tile or the
+        six faces alike: d["u_dt"], d["v_dt"] are zeroed as the reference zeroes them, K_warm_rain updates pt, delp, the tracers
+        sphum, liq_wat, rainwat of the moist dict, ua, va, w in place, rebuilds pe, peln, pk, ps and writes d["rain"] [kg/dA].  With
+        K_sedi_transport fv_update_phys follows with the resident u_dt, v_dt and zero t_dt, q_dt (:499: no_tendency false);
+        otherwise nothing follows.  moist_kappa is the flags'.  Not applied: the do_terminator rescaling of :476-515.  No
+        field leaves the device."""
+        d, ctx, fl = self.dc.d, self.ctx, self.fl
+        npz = ctx.npz
+        sp = {n: int(self.sg_species.get(n, 0) or 0) for n in ("sphum", "liq_wat", "rainwat")}
+        if not all(1 <= v <= self.nq for v in sp.values()):
+            raise ValueError(f"FvDynamics.k_warm_rain: the moist dict names {sp}; K_warm_rain reads sphum, liq_wat and rainwat of 1..{self.nq}")
+        for n in ("u_dt", "v_dt"):                                          # :292-313
+            if n not in d:
+                d[n] = ctx.zeros("A", npz)
+            else:
+                d[n].zero()
+        if "rain" not in d:
+            d["rain"] = ctx.zeros("CC")
+        hyd = fl.hydrostatic
+        k = dict(dict(self.neg_adj_consts, kappa=fl.akap), **(consts or {}))
+        ctx.k_warm_rain(dt, d["ua"], d["va"], None if hyd else d["w"], d["u_dt"], d["v_dt"], d["q"], d["pt"], d["delp"],
+                        None if hyd else d["delz"], d["pe"], d["peln"], d["pk"], d["ps"], d["rain"], self.nq, sphum=sp["sphum"],
+                        liq_wat=sp["liq_wat"], rainwat=sp["rainwat"], K_cycle=K_cycle, K_sedi_transport=K_sedi_transport,
+                        do_K_sedi_w=do_K_sedi_w, do_K_sedi_heat=do_K_sedi_heat, hydrostatic=hyd, moist_kappa=bool(fl.moist_kappa), consts=k)
+        if K_sedi_transport:                                               # :499, :675-687
+            if "t_dt" not in d:
+                d["t_dt"] = ctx.zeros("CC", npz)
+            else:
+                d["t_dt"].zero()
+            if "q_dt" not in d:
+                d["q_dt"] = ctx.from_host(np.zeros((ctx.bd.nx, ctx.bd.ny, npz, self.nq), order="F"))
+            else:
+                d["q_dt"].zero()
+            self.fv_update_phys(dt, d["t_dt"], d["q_dt"], d["u_dt"], d["v_dt"])
+
+    def supercell_step(self, bdt: float, **kessler):
+        """atmosphere_step followed by k_warm_rain: one step of the supercell case with its microphysics (the solo driver's
+        atmosphere_dynamics and fv_phys with do_K_warm_rain)"""
+        self.atmosphere_step(bdt)
+        self.k_warm_rain(bdt, **kessler)
+
     # -- neg_adj3 -------------------------------------------------------------------------------------------------
     def _prt_negative(self, when: str):
         """prt_negative (fv_sg.F90:1372-1392) of T and the six species: the global minimum, reported when below its threshold"""

@@ -40,7 +40,7 @@ EXPORTS = ["fv3_last_error", "fv3_create", "fv3_destroy", "fv3_set_stream", "fv3
            "fv3_fv_subgrid_z", "fv3_grid_upload_dwinds", "fv3_update_dwinds_phys", "fv3_interpolate_vertical", "fv3_fv_update_phys",
            "fv3_grid_upload_lat", "fv3_held_suarez_tend", "fv3_age_of_air",
            "fv3_grid_upload_reed", "fv3_grid_download_reed", "fv3_reed_sim_phys", "fv3_grid_upload_terminator", "fv3_grid_download_terminator",
-           "fv3_terminator_advance"]
+           "fv3_terminator_advance", "fv3_qs_wat_init", "fv3_qs_wat_download", "fv3_k_warm_rain"]
 
 
 class Fv3Error(RuntimeError):
@@ -189,6 +189,26 @@ REED_CONSTS = dict(grav=GRAV, rdgas=RDGAS, rvgas=461.50, cp_air=CP_AIR, cp_vapor
 def _reed_consts(consts):
     k = dict(REED_CONSTS, **{n: v for n, v in (consts or {}).items() if n in REED_CONSTS})
     return _ReedConsts(*(float(k[n]) for n, _ in _ReedConsts._fields_))
+
+
+class _KesslerConsts(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ["rdgas", "rvgas", "cp_air", "cp_vapor", "hlv", "c_liq", "grav", "kappa"]]
+
+
+class _KesslerParams(C.Structure):
+    _fields_ = [("pdt", C.c_double)] + [(n, C.c_int) for n in ["K_cycle", "K_sedi_transport", "do_K_sedi_w", "do_K_sedi_heat", "hydrostatic",
+                                                                "moist_kappa", "nq", "sphum", "liq_wat", "rainwat"]] + [("k", _KesslerConsts)]
+
+
+# what K_warm_rain, kessler_imp and qs_tables_mod (driver/solo/fv_phys.F90:74-85, :1992-2291; qs_tables.F90:24-43) take from constants_mod
+# and gfdl_mp_mod
+KESSLER_CONSTS = dict(rdgas=RDGAS, rvgas=461.50, cp_air=CP_AIR, cp_vapor=4.0 * 461.50, hlv=2.500e6, c_liq=4.218e3, grav=GRAV, kappa=RDGAS / CP_AIR)
+QS_LENGTH = 2621
+
+
+def _kessler_consts(consts):
+    k = dict(KESSLER_CONSTS, **{n: v for n, v in (consts or {}).items() if n in KESSLER_CONSTS})
+    return _KesslerConsts(*(float(k[n]) for n, _ in _KesslerConsts._fields_))
 
 
 SG_SPECIES = ("sphum", "liq_wat", "rainwat", "ice_wat", "snowwat", "graupel")
@@ -613,6 +633,33 @@ class Context:
         self.lib.check(self.lib.dll.fv3_reed_sim_phys(self.h, C.byref(pr), _pp(delp), _pp(pt), _pp(ua), _pp(va), _pp(q), _pp(pe), _pp(peln),
                                                       _pp(phis), _pp(delz), _pp(u_dt), _pp(v_dt), _pp(t_dt), _pp(q_dt), _pp(rain)),
                        "fv3_reed_sim_phys")
+
+    def qs_wat_init(self, consts=None):
+        """fv3_qs_wat_init: table_w and des_w of qs_tables_mod (driver/solo/qs_tables.F90:95-132), formed on the host and uploaded.
+        consts: overrides of KESSLER_CONSTS."""
+        k = _kessler_consts(consts)
+        self.lib.check(self.lib.dll.fv3_qs_wat_init(self.h, C.byref(k)), "fv3_qs_wat_init")
+        self.qs_wat_ready = tuple(getattr(k, n) for n, _ in _KesslerConsts._fields_)
+
+    def qs_wat_download(self):
+        """fv3_qs_wat_download -> (table_w, des_w), 2621 each, as fv3_qs_wat_init formed them"""
+        tw, dw = np.zeros(QS_LENGTH), np.zeros(QS_LENGTH)
+        self.lib.check(self.lib.dll.fv3_qs_wat_download(self.h, tw.ctypes.data_as(_dp), dw.ctypes.data_as(_dp)), "fv3_qs_wat_download")
+        return tw, dw
+
+    def k_warm_rain(self, pdt, ua, va, w, u_dt, v_dt, q, pt, delp, delz, pe, peln, pk, ps, rain, nq, sphum=1, liq_wat=2, rainwat=3, K_cycle=0,
+                    K_sedi_transport=False, do_K_sedi_w=False, do_K_sedi_heat=False, hydrostatic=False, moist_kappa=False, consts=None):
+        """K_warm_rain with kessler_imp inside it (driver/solo/fv_phys.F90:1992-2291): the Kessler warm-rain microphysics on the state in
+        place.  q: the whole tracer array (A x npz x nq); sphum, liq_wat, rainwat: 1-based planes of it.  pt is the temperature.  rain
+        (is:ie, js:je) is written in every cell [kg/dA].  K_cycle = 0: max(1, nint(pdt/30.)).  delz may be None when hydrostatic without
+        do_K_sedi_heat, w unless K_sedi_transport and do_K_sedi_w.  The table is formed on first use, or when the constants change."""
+        k = _kessler_consts(consts)
+        if getattr(self, "qs_wat_ready", None) != tuple(getattr(k, n) for n, _ in _KesslerConsts._fields_):
+            self.qs_wat_init(consts)
+        pr = _KesslerParams(float(pdt), int(K_cycle), int(bool(K_sedi_transport)), int(bool(do_K_sedi_w)), int(bool(do_K_sedi_heat)),
+                            int(bool(hydrostatic)), int(bool(moist_kappa)), int(nq), int(sphum), int(liq_wat), int(rainwat), k)
+        self.lib.check(self.lib.dll.fv3_k_warm_rain(self.h, C.byref(pr), _pp(ua), _pp(va), _pp(w), _pp(u_dt), _pp(v_dt), _pp(q), _pp(pt), _pp(delp),
+                                                    _pp(delz), _pp(pe), _pp(peln), _pp(pk), _pp(ps), _pp(rain)), "fv3_k_warm_rain")
 
     def grid_upload_terminator(self, agrid=None, pi=REED_CONSTS["pi"]):
         """fv3_grid_upload_terminator: k1 of DCMIP2016_terminator_advance (driver/solo/fv_phys.F90:2873) over the A layout, formed on the

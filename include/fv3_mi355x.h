@@ -870,6 +870,63 @@ int fv3_grid_download_terminator(fv3_ctx *ctx, double *k1);
  * r*r + 2 r (Cl + 2 Cl2) < 0 (the square root of a negative number). */
 int fv3_terminator_advance(fv3_ctx *ctx, int km, double pdt, int term_fill_negative, double *cl, double *cl2);
 
+/* fv3_qs_wat_init -- qs_wat_init and qs_table_w, driver/solo/qs_tables.F90:95-132: the saturation vapour pressure over water,
+ * table_w(2621), and its differences des_w(2621), 0.1 K apart from tmin = tice - 160.  The host forms both with its libm in the
+ * reference's own expressions -- tem = tmin + 0.1*real(i-1), table_w(i) = e0*exp((dc_vap*log(tem/tice) + Lv0*(tem-tice)/(tem*tice))/
+ * rvgas), des_w(i) = max(0., table_w(i+1) - table_w(i)), the last entry copied -- with e0 = 610.71, tice = 273.16, dc_vap =
+ * cp_vapor - c_liq (the non-SIM_NGGPS build) and Lv0 = hlv - dc_vap*tice of :32-43, and uploads them to the context.  Read of k:
+ * rvgas, cp_vapor, c_liq, hlv.  Written: the context's table and the constants it was formed with, nothing else.  Refused: null
+ * arguments, a constant of rdgas, rvgas, cp_air, grav, kappa that is not positive.  A second call replaces the table (queued
+ * launches of an fv3_group run first).  The table has entry points of its own because do_LS_cond (fv_phys.F90:392-464, not built)
+ * reads it as well. */
+typedef struct fv3_kessler_consts {
+  double rdgas, rvgas, cp_air, cp_vapor, hlv;    /* constants_mod's */
+  double c_liq;                                  /* gfdl_mp.F90:137 */
+  double grav, kappa;                            /* constants_mod's */
+} fv3_kessler_consts;
+int fv3_qs_wat_init(fv3_ctx *ctx, const fv3_kessler_consts *k);
+/* fv3_qs_wat_download -- the two arrays fv3_qs_wat_init formed, back on the host: table_w, des_w, 2621 doubles each, HOST.  For
+ * checks: both are held bit for bit to the reference's compiler.  Refused: null arguments, no table. */
+int fv3_qs_wat_download(fv3_ctx *ctx, double *table_w, double *des_w);
+
+/* fv3_k_warm_rain -- K_warm_rain, driver/solo/fv_phys.F90:1992-2196, with kessler_imp (:2202-2291) inside it and qs_wat of
+ * driver/solo/qs_tables.F90:67-93: the Kessler warm-rain microphysics of the solo driver's do_K_warm_rain branch (:466-499), the
+ * physics of the supercell case.  It changes the state in place.  One launch (six faces of an fv3_group: one), one thread per
+ * column, ONE downward sweep per cycle: level k needs of level k-1 the rain after sedimentation and before the microphysics, r,
+ * vr, the running sum m1 and the updated u1, v1, t1, all in registers; rho(nz) (:2234) is formed once before the first sweep.
+ * Between cycles t1, q1, q2, q3, u1, v1, w1, drym, dz, qa, qb, qc live in twelve work planes of the context (12 x (is:ie, js:je,
+ * npz)), under the poison contract (FV3_MI355X_POISON): written by the first cycle before any later one reads them, nothing carried
+ * between calls; with K_cycle = 1 none is touched or allocated.  The last sweep writes the outputs (:2156-2173) and rebuilds pe,
+ * peln, pk, ps (:2177-2186).  log, exp are include/fv3_math.h, x**y is exp of y log x from the same header (0 at x = 0), sqrt is
+ * correctly rounded; the scalars are formed on the host in the reference's expressions from the constants in k.
+ * K_cycle: the number of cycles; 0 = max(1, nint(pdt/30.)), formed on the host as :472-474 does.  sphum, liq_wat, rainwat: 1-based
+ * planes of q.  do_K_sedi_w is read only with K_sedi_transport (:2114-2116).
+ * ua, va, w, u_dt, v_dt, pt (the temperature), delp: A x npz; q: A x npz x nq; delz (is:ie, js:je, npz); pe (is-1:ie+1, npz+1,
+ * js-1:je+1); peln (is:ie, npz+1, js:je); pk (is:ie, js:je, npz+1); ps: A; rain (is:ie, js:je).  Device pointers.
+ * Read: delp, pt, the three planes of q, u_dt, v_dt, ua, va; pe(1); peln when hydrostatic, delz when not or with do_K_sedi_heat;
+ * w with K_sedi_transport and do_K_sedi_w.
+ * Written, on the compute domain only: pt, delp, the three planes of q, u_dt, v_dt (each plus (u1 - u)/pdt: +0 without
+ * K_sedi_transport); ua, va with K_sedi_transport and w with do_K_sedi_w too (without, the reference writes them back with their
+ * own bits: they are not touched, and w may be NULL); pe, peln, pk on levels 2 .. npz+1, ps; rain [kg/dA] summed over the cycles
+ * (:2112), every cell.  Halos, the other tracers, level 1 of pe, peln, pk and the ring of pe keep their bits.
+ * Refused (status 1 and a message, nothing launched): null fields; npz < 1; pdt <= 0; K_cycle < 0; no table uploaded
+ * (fv3_qs_wat_init), or one uploaded with other constants; tracer indices outside 1..nq or not distinct; delz NULL when not
+ * hydrostatic or with do_K_sedi_heat (:2137 reads it either way); w NULL with K_sedi_transport and do_K_sedi_w.
+ * qs_wat's second index it = ap1 - 0.5 is 0 for ta < tmin + 0.05 K, where the reference reads the word before des_w: the library
+ * takes 0. there and reads nothing outside the table.
+ * Not built: id_vr_k / send_data, prec_total and its g_sum, the SIM_NGGPS build, the do_terminator rescaling of :476-515 (two
+ * pointwise multiplies the caller has), do_LS_cond. */
+typedef struct fv3_kessler_params {
+  double pdt;                                        /* the physics step [s] */
+  int K_cycle;                                       /* 0: max(1, nint(pdt/30.)) */
+  int K_sedi_transport, do_K_sedi_w, do_K_sedi_heat;
+  int hydrostatic, moist_kappa;
+  int nq, sphum, liq_wat, rainwat;                   /* the planes of q and the three the routine reads, 1-based */
+  fv3_kessler_consts k;
+} fv3_kessler_params;
+int fv3_k_warm_rain(fv3_ctx *ctx, const fv3_kessler_params *p, double *ua, double *va, double *w, double *u_dt, double *v_dt, double *q,
+                    double *pt, double *delp, const double *delz, double *pe, double *peln, double *pk, double *ps, double *rain);
+
 /* fv3_interpolate_vertical -- interpolate_vertical, tools/fv_diagnostics.F90:4910-4948 (call sites :2017 the 850 hPa vorticity, :2198 and :2263-2299
  * the relative humidity at 200 hPa and at ten CMIP levels, :2971-2979 condensate at 200 / 500 / 850 hPa, :3522): the field a3 (km layers) at the one pressure plev [Pa], linear in the layer-mean log pressure
  * pm(k) = 0.5 (peln(k) + peln(k+1)) (:4930); at or above pm(1) it is a3(1), at or below pm(km) it is a3(km) (:4933-4936).
