@@ -4440,6 +4440,53 @@ extern "C" int fv3_fill2d_apply(fv3_ctx *c, int nk, const double *qt, const doub
   return 0;
 }
 
+// ---- entry helpers of the column-physics packages (neg_adj3 ... K_warm_rain below) -------------------------------------------------
+// Replace a device table that the host forms, n doubles.  A launch that an fv3_group still holds reads the old table: where the slot
+// exists the queues run, and the stream drains, before the table changes; the upload has landed when this returns.
+static int table_replace(fv3_ctx *c, double **slot, const double *host, size_t n) {
+  if (*slot) {
+    if (int rc = grp_flush_all()) return rc;
+    RT(rtf_sync(c->stream));
+  } else {
+    RT(rt_malloc((void **)slot, n * sizeof(double)));
+  }
+  RT(rtf_h2d(*slot, host, n * sizeof(double), c->stream));
+  RT(rtf_sync(c->stream));
+  return 0;
+}
+
+// One lane per column of the compute domain, whole columns in registers: blocks of CH = 256 over nx * ny.
+template <class K>
+static int launch_col(fv3_ctx *c, const char *label, const K &kf) {
+  static_assert(K::CH == 256, "col_grid");
+  return launch_p(c, label, col_grid(c->g.nx * c->g.ny), 0, kf);
+}
+
+// Runtime flags to template arguments: with_consts(f, a, b, ...) calls the generic lambda f with one constant per argument, a
+// std::bool_constant for a bool and a std::integral_constant<int, V> for a one_of<Vs...>, whose last V stands for every value not
+// listed.  f is instantiated for the whole product of the arguments' values, so flags that only matter together go in as one one_of.
+template <int... Vs>
+struct one_of {
+  int v;
+};
+template <class F>
+static int with_consts(const F &f) {
+  return f();
+}
+template <class F, class... R>
+static int with_consts(const F &f, bool b, R... rest);
+template <class F, int V0, int... Vs, class... R>
+static int with_consts(const F &f, one_of<V0, Vs...> s, R... rest) {
+  if constexpr (sizeof...(Vs) > 0)
+    if (s.v != V0) return with_consts(f, one_of<Vs...>{s.v}, rest...);
+  return with_consts([&](auto... r) -> int { return f(std::integral_constant<int, V0>{}, r...); }, rest...);
+}
+template <class F, class... R>
+static int with_consts(const F &f, bool b, R... rest) {
+  if (b) return with_consts([&](auto... r) -> int { return f(std::true_type{}, r...); }, rest...);
+  return with_consts([&](auto... r) -> int { return f(std::false_type{}, r...); }, rest...);
+}
+
 extern "C" int fv3_neg_adj3(fv3_ctx *c, const fv3_neg_adj_params *p, const double *peln, const double *delz, const double *delp,
                             double *pt, double *qv, double *ql, double *qr, double *qi, double *qs, double *qg, double *qa) {
   FV3_ENTRY(c);
@@ -4451,11 +4498,7 @@ extern "C" int fv3_neg_adj3(fv3_ctx *c, const fv3_neg_adj_params *p, const doubl
   if (g.npz < 2) return fail("fv3_neg_adj3: the vertical borrowing needs npz >= 2");
   NegAdj3 kf{g, g.npz, p->hydrostatic ? 1 : 0, p->rdgas, p->rvgas, p->cp_air, p->cp_vapor, p->hlv, p->hlf, p->c_liq, p->c_ice,
              delp, pt, qv, ql, qr, qi, qs, qg, qa};
-  Dim3 grid;
-  grid.x = (unsigned)(((size_t)g.nx * g.ny + NegAdj3::CH - 1) / NegAdj3::CH);
-  grid.y = 1;
-  grid.z = 1;
-  RT(launch_p(c, "neg_adj3", grid, 0, kf));
+  RT(launch_col(c, "neg_adj3", kf));
   return 0;
 }
 
@@ -4506,30 +4549,15 @@ extern "C" int fv3_fv_subgrid_z(fv3_ctx *c, const fv3_sg_params *p, const double
     RT(work_alloc(c, "sg_wk", 0, &c->sg_wk, need));
     c->sg_wk_n = need;
   }
-  Dim3 grid;
-  grid.x = (unsigned)(((size_t)g.nx * g.ny + 255) / 256);
-  grid.y = 1;
-  grid.z = 1;
   auto go = [&](auto H, auto NWc) -> int {
     FvSubgridZ<decltype(H)::value, decltype(NWc)::value> kf{
         g, kbot, p->k_bot_full, p->nq, p->sphum - 1, p->liq_wat - 1, p->rainwat - 1, p->ice_wat - 1, p->snowwat - 1, p->graupel - 1, fra_full,
         fra_weak, 1. / p->dt, t_max, t_min, p->rdgas, p->rvgas, p->grav, p->cp_air, p->cp_vapor, p->c_liq, p->c_ice, delp, pe, peln, pkz, delz,
         ta, qa, ua, va, w, u_dt, v_dt, c->sg_wk};
-    static_assert(decltype(kf)::CH == 256, "grid.x above");
-    return launch_p(c, "fv_subgrid_z", grid, 0, kf);
+    return launch_col(c, "fv_subgrid_z", kf);
   };
-  auto by_nwat = [&](auto H) -> int {   // the branch set of fv_sg.F90:214-249: 0, 1, 2, 3, 4, everything else as 6
-    switch (nw) {
-      case 0: return go(H, std::integral_constant<int, 0>{});
-      case 1: return go(H, std::integral_constant<int, 1>{});
-      case 2: return go(H, std::integral_constant<int, 2>{});
-      case 3: return go(H, std::integral_constant<int, 3>{});
-      case 4: return go(H, std::integral_constant<int, 4>{});
-      default: return go(H, std::integral_constant<int, 6>{});
-    }
-  };
-  if (p->hydrostatic) RT(by_nwat(std::true_type{}));
-  else RT(by_nwat(std::false_type{}));
+  const one_of<0, 1, 2, 3, 4, 6> by_nwat{nw};   // the branch set of fv_sg.F90:214-249: 0, 1, 2, 3, 4, everything else as 6
+  RT(with_consts(go, p->hydrostatic != 0, by_nwat));
   return 0;
 }
 
@@ -4662,15 +4690,8 @@ extern "C" int fv3_fv_update_phys(fv3_ctx *c, const fv3_update_phys_params *p, c
       tab[k] = qstar;
       tab[npz + k] = fac;
     }
-    if (tab != c->up_tab_host) {   // a launch that an fv3_group still holds reads the old table: the queues run before it changes
-      if (c->up_tab) {
-        if (int rc = grp_flush_all()) return rc;
-        RT(rtf_sync(c->stream));
-      } else {
-        RT(rt_malloc((void **)&c->up_tab, tab.size() * sizeof(double)));
-      }
-      RT(rtf_h2d(c->up_tab, tab.data(), tab.size() * sizeof(double), c->stream));
-      RT(rtf_sync(c->stream));
+    if (tab != c->up_tab_host) {   // only this table is re-formed by every call: uploaded when the host copy differs
+      if (int rc = table_replace(c, &c->up_tab, tab.data(), tab.size())) return rc;
       c->up_tab_host = tab;
     }
     qstar_dev = c->up_tab;
@@ -4681,23 +4702,12 @@ extern "C" int fv3_fv_update_phys(fv3_ctx *c, const fv3_update_phys_params *p, c
         g, p->nq, p->ncnst, nw, p->sphum - 1, p->liq_wat - 1, p->rainwat - 1, p->ice_wat - 1, p->snowwat - 1, p->graupel - 1, w_diff - 1, adj,
         has_qdt ? 1 : 0, relax ? 1 : 0, p->gfs_phys ? 0 : 1, p->dt, p->ptop, p->kappa, p->rdgas, p->rvgas, p->grav, p->cp_air, p->cp_vapor,
         p->c_liq, p->c_ice, qstar_dev, pfac_dev, t_dt, u_dt, v_dt, q_dt, q, qdiag, delp, pt, delz, ua, va, ps, pe, peln, pk, pkz, u_srf, v_srf};
-    static_assert(decltype(kf)::CH == 256, "col_grid");
-    return launch_p(c, "fv_update_phys", col_grid(g.nx * g.ny), 0, kf);
+    return launch_col(c, "fv_update_phys", kf);
   };
-  auto by_nwat = [&](auto TBc) -> int {   // fv_thermodynamics.F90:262-323, :340-402
-    switch (nwc) {
-      case 2: return go(TBc, std::integral_constant<int, 2>{});
-      case 3: return go(TBc, std::integral_constant<int, 3>{});
-      case 4: return go(TBc, std::integral_constant<int, 4>{});
-      case 5: return go(TBc, std::integral_constant<int, 5>{});
-      case 6: return go(TBc, std::integral_constant<int, 6>{});
-      default: return go(TBc, std::integral_constant<int, 0>{});
-    }
-  };
-  if (tb == 0) RT(by_nwat(std::integral_constant<int, 0>{}));
-  else if (tb == 1) RT(by_nwat(std::integral_constant<int, 1>{}));
-  else if (tb == 2) RT(go(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}));
-  else RT(by_nwat(std::integral_constant<int, 3>{}));
+  const one_of<0, 1, 3> by_tb{tb};
+  const one_of<2, 3, 4, 5, 6, 0> by_nwat{nwc};   // fv_thermodynamics.F90:262-323, :340-402
+  if (tb == 2) RT(go(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}));   // nwc = 0: the gama_dt branch calls neither
+  else RT(with_consts(go, by_tb, by_nwat));
   return 0;
 }
 
@@ -4719,14 +4729,7 @@ extern "C" int fv3_grid_upload_lat(fv3_ctx *c, const double *lat) {
     tab[3 * nc + n] = tz * (ap0k / akap) * std::cos(a) * std::cos(a);
     tab[4 * nc + n] = std::pow(std::cos(a), 4.0);
   }
-  if (c->hs_lat) {   // a launch that an fv3_group still holds reads the old table: the queues run before it changes
-    if (int rc = grp_flush_all()) return rc;
-    RT(rtf_sync(c->stream));
-  } else {
-    RT(rt_malloc((void **)&c->hs_lat, tab.size() * sizeof(double)));
-  }
-  RT(rtf_h2d(c->hs_lat, tab.data(), tab.size() * sizeof(double), c->stream));
-  RT(rtf_sync(c->stream));
+  if (int rc = table_replace(c, &c->hs_lat, tab.data(), tab.size())) return rc;
   return 0;
 }
 
@@ -4768,16 +4771,9 @@ extern "C" int fv3_held_suarez_tend(fv3_ctx *c, const fv3_held_suarez_params *p,
   auto go = [&](auto S, auto Z) -> int {
     HeldSuarezTend<decltype(S)::value, decltype(Z)::value> kf{g, p->fresh ? 1 : 0, pdt, sday, rdt, rkv, rka, rks - rka, rms, rmr, tau, t_ms, rsgb,
                                                                ap0k, algpk, rd_zur_rad, c->hs_lat, delp, peln, pe, pkz, pt, ua, va, u_dt, v_dt, t_dt};
-    static_assert(decltype(kf)::CH == 256, "col_grid");
-    return launch_p(c, "held_suarez_tend", col_grid(g.nx * g.ny), 0, kf);
+    return launch_col(c, "held_suarez_tend", kf);
   };
-  if (p->strat) {
-    if (p->zurita) RT(go(std::true_type{}, std::true_type{}));
-    else RT(go(std::true_type{}, std::false_type{}));
-  } else {
-    if (p->zurita) RT(go(std::false_type{}, std::true_type{}));
-    else RT(go(std::false_type{}, std::false_type{}));
-  }
+  RT(with_consts(go, p->strat != 0, p->zurita != 0));
   return 0;
 }
 
@@ -4790,8 +4786,7 @@ extern "C" int fv3_age_of_air(fv3_ctx *c, int km, double time, const double *pe,
   const Grid &g = c->g;
   const double tiny = 1.e-6, ascale = 5.e-6 / 60.;   // hswf.F90:228-230
   AgeOfAir kf{g, km, time < tiny ? 1 : 0, ascale * time, pe, q};
-  static_assert(AgeOfAir::CH == 256, "col_grid");
-  RT(launch_p(c, "age_of_air", col_grid(g.nx * g.ny), 0, kf));
+  RT(launch_col(c, "age_of_air", kf));
   return 0;
 }
 
@@ -4844,14 +4839,7 @@ extern "C" int fv3_grid_upload_reed(fv3_ctx *c, const double *lat, int reed_test
     tab[n] = Tsurf;
     tab[nc + n] = std::exp((dc_vap * std::log(Tsurf / tice) + Lv0 * (Tsurf - tice) / (Tsurf * tice)) / k->rvgas);   // :2719
   }
-  if (c->reed_tab) {   // a launch that an fv3_group still holds reads the old table: the queues run before it changes
-    if (int rc = grp_flush_all()) return rc;
-    RT(rtf_sync(c->stream));
-  } else {
-    RT(rt_malloc((void **)&c->reed_tab, tab.size() * sizeof(double)));
-  }
-  RT(rtf_h2d(c->reed_tab, tab.data(), tab.size() * sizeof(double), c->stream));
-  RT(rtf_sync(c->stream));
+  if (int rc = table_replace(c, &c->reed_tab, tab.data(), tab.size())) return rc;
   c->reed_tab_test = reed_test;
   return 0;
 }
@@ -4903,20 +4891,14 @@ extern "C" int fv3_reed_sim_phys(fv3_ctx *c, const fv3_reed_params *p, const dou
   s.rgrav = 1. / p->k.grav;
   s.rdrg = p->k.rdgas * s.rgrav;
   s.zvir_w = p->k.rvgas / p->k.rdgas - 1.;
-  auto go = [&](auto Cn, auto A, auto H) -> int {
-    ReedSimPhys<decltype(Cn)::value, decltype(A)::value, decltype(H)::value> kf{g, p->fresh ? 1 : 0, p->reed_test, p->reed_cond_only ? 1 : 0, s,
-                                                                               c->reed_tab, delp, pt, ua, va, q, pe, peln, phis, delz, u_dt, v_dt,
-                                                                               t_dt, q_dt, rain, c->reed_wk};
-    static_assert(decltype(kf)::CH == 256, "col_grid");
-    return launch_p(c, "reed_sim_phys", col_grid(g.nx * g.ny), 0, kf);
+  auto go = [&](auto Cn, auto Z) -> int {   // Z: 0 no reed_alt_mxg, 1 reed_alt_mxg with a hydrostatic zint, 2 with zint from delz
+    ReedSimPhys<decltype(Cn)::value, (decltype(Z)::value >= 1), (decltype(Z)::value != 2)> kf{
+        g, p->fresh ? 1 : 0, p->reed_test, p->reed_cond_only ? 1 : 0, s, c->reed_tab, delp, pt, ua, va, q, pe, peln, phis, delz, u_dt, v_dt,
+        t_dt, q_dt, rain, c->reed_wk};
+    return launch_col(c, "reed_sim_phys", kf);
   };
-  auto alt = [&](auto Cn) -> int {   // hydrostatic is read only where reed_alt_mxg builds zint
-    if (!p->reed_alt_mxg) return go(Cn, std::false_type{}, std::true_type{});
-    if (p->hydrostatic) return go(Cn, std::true_type{}, std::true_type{});
-    return go(Cn, std::true_type{}, std::false_type{});
-  };
-  if (p->do_reed_cond) RT(alt(std::true_type{}));
-  else RT(alt(std::false_type{}));
+  const one_of<0, 1, 2> zint{!p->reed_alt_mxg ? 0 : (p->hydrostatic ? 1 : 2)};   // hydrostatic is read only where reed_alt_mxg builds zint
+  RT(with_consts(go, p->do_reed_cond != 0, zint));
   return 0;
 }
 
@@ -4932,14 +4914,7 @@ extern "C" int fv3_grid_upload_terminator(fv3_ctx *c, const double *agrid, doubl
     const double lon = agrid[n], lat = agrid[n2 + n];
     k1[n] = std::fmax(0., std::sin(lat) * sinthc + std::cos(lat) * costhc * std::cos(lon - lc));   // :2873
   }
-  if (c->term_k1) {
-    if (int rc = grp_flush_all()) return rc;
-    RT(rtf_sync(c->stream));
-  } else {
-    RT(rt_malloc((void **)&c->term_k1, n2 * sizeof(double)));
-  }
-  RT(rtf_h2d(c->term_k1, k1.data(), n2 * sizeof(double), c->stream));
-  RT(rtf_sync(c->stream));
+  if (int rc = table_replace(c, &c->term_k1, k1.data(), n2)) return rc;
   return 0;
 }
 
@@ -5001,14 +4976,7 @@ extern "C" int fv3_qs_wat_init(fv3_ctx *c, const fv3_kessler_consts *k) {
   }
   for (int i = 1; i <= kQsLen - 1; i++) des_w[i - 1] = std::fmax(0., table_w[i] - table_w[i - 1]);   // :106-109
   des_w[kQsLen - 1] = des_w[kQsLen - 2];
-  if (c->qs_tab) {   // a launch that an fv3_group still holds reads the old table: the queues run before it changes
-    if (int rc = grp_flush_all()) return rc;
-    RT(rtf_sync(c->stream));
-  } else {
-    RT(rt_malloc((void **)&c->qs_tab, tab.size() * sizeof(double)));
-  }
-  RT(rtf_h2d(c->qs_tab, tab.data(), tab.size() * sizeof(double), c->stream));
-  RT(rtf_sync(c->stream));
+  if (int rc = table_replace(c, &c->qs_tab, tab.data(), tab.size())) return rc;
   c->qs_consts = *k;
   return 0;
 }
@@ -5069,21 +5037,14 @@ extern "C" int fv3_k_warm_rain(fv3_ctx *c, const fv3_kessler_params *p, double *
   s.tmin = tice - 160.;
   s.hg = 0.5 * p->k.grav;
   s.sdt22 = s.sdt * 2.2;
-  auto go = [&](auto H, auto M, auto T, auto W, auto E) -> int {
-    KWarmRain<decltype(H)::value, decltype(M)::value, decltype(T)::value, decltype(W)::value, decltype(E)::value> kf{
+  auto go = [&](auto H, auto M, auto S, auto E) -> int {   // S: 0 no sedimentation transport, 1 transport, 2 transport with w
+    KWarmRain<decltype(H)::value, decltype(M)::value, (decltype(S)::value >= 1), (decltype(S)::value == 2), decltype(E)::value> kf{
         g, ncyc, p->sphum - 1, p->liq_wat - 1, p->rainwat - 1, s, c->qs_tab, c->qs_tab + kQsLen, ua, va, w, u_dt, v_dt, q, pt, delp, delz,
         pe, peln, pk, ps, rain, ncyc > 1 ? c->kessler_wk : nullptr};
-    static_assert(decltype(kf)::CH == 256, "col_grid");
-    return launch_p(c, "k_warm_rain", col_grid(g.nx * g.ny), 0, kf);
+    return launch_col(c, "k_warm_rain", kf);
   };
-  auto heat = [&](auto H, auto M, auto T, auto W) -> int { return sh ? go(H, M, T, W, std::true_type{}) : go(H, M, T, W, std::false_type{}); };
-  auto trans = [&](auto H, auto M) -> int {   // do_K_sedi_w is read only inside K_sedi_transport
-    if (!tr) return heat(H, M, std::false_type{}, std::false_type{});
-    return sw ? heat(H, M, std::true_type{}, std::true_type{}) : heat(H, M, std::true_type{}, std::false_type{});
-  };
-  auto mk = [&](auto H) -> int { return p->moist_kappa ? trans(H, std::true_type{}) : trans(H, std::false_type{}); };
-  if (p->hydrostatic) RT(mk(std::true_type{}));
-  else RT(mk(std::false_type{}));
+  const one_of<0, 1, 2> sedi{tr ? (sw ? 2 : 1) : 0};   // do_K_sedi_w is read only inside K_sedi_transport
+  RT(with_consts(go, p->hydrostatic != 0, p->moist_kappa != 0, sedi, sh));
   return 0;
 }
 

@@ -16,11 +16,10 @@ longitudes are noise.
 """
 from __future__ import annotations
 
-import hashlib
-
 import numpy as np
 
 from gfdl_atmos_cubed_sphere_amd.layout import Bounds
+from parity_phys import checksum  # noqa: F401
 
 KAPPA = 2.0 / 7.0
 PI = 3.14159265358979323846       # constants_mod's pi
@@ -92,14 +91,6 @@ def state(nx, ny, km, seed, zero_tendencies=False):
         for n in OUT:
             st[n][...] = 0.0
     return bd, st
-
-
-def checksum(st):
-    h = hashlib.sha256()
-    for n in sorted(st):
-        h.update(n.encode())
-        h.update(np.ascontiguousarray(st[n]).tobytes())
-    return h.hexdigest()
 
 
 # ---- the recorded cases: 6 x 4 columns.  Per (strat, zurita) set -- the golden file tests/golden/held_suarez_<set>.npz --: km 1, 2, 12,

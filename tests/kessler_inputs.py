@@ -21,11 +21,10 @@ are noise.
 """
 from __future__ import annotations
 
-import hashlib
-
 import numpy as np
 
 from gfdl_atmos_cubed_sphere_amd.layout import Bounds
+from parity_phys import checksum  # noqa: F401
 
 KAPPA = 2.0 / 7.0
 # the reference's constants_mod (GFDL defaults) and gfdl_mp_mod's c_liq: what tests/golden/kessler_ref/kessler_standins.F90 states
@@ -106,14 +105,6 @@ def state(nx, ny, km, seed, hydrostatic=False, nq=NQ, tracers=(1, 2, 3)):
               q=halo(q4), pt=halo(T), delp=halo(dpc), delz=F(dz), pe=pe, peln=F(np.transpose(peln_c, (0, 2, 1))),
               pk=F(np.exp(KAPPA * peln_c)), ps=halo(ps), rain=F(rng.uniform(1.0, 2.0, (nx, ny))))
     return bd, st
-
-
-def checksum(st):
-    h = hashlib.sha256()
-    for n in sorted(st):
-        h.update(n.encode())
-        h.update(np.ascontiguousarray(st[n]).tobytes())
-    return h.hexdigest()
 
 
 # ---- the recorded cases: 12 x 7 columns; km 1, 2, 12 x (hydrostatic, not) x moist_kappa (on, off) x the five flag sets, and km 32 x

@@ -7,29 +7,21 @@ Bound: no exp or log runs on the device (log(plev) is the host's), so the librar
 from __future__ import annotations
 
 import ctypes as C
-import functools
-import os
 
 import numpy as np
 
 import diag_inputs as DI
 import parity_common as P
+import parity_phys as H
 import ref_fv_diag as R
-from gfdl_atmos_cubed_sphere_amd.lib import Context, Fv3Error
+from gfdl_atmos_cubed_sphere_amd.lib import Context
 from memory_contract import host_out
+from parity_phys import compute as cc, same_bits as bits_equal
 
 SHAPES = ((21, 7), (40, 19), (130, 100))      # no multiple of the wavefront; 40 x 19 and 130 x 100 cross a workgroup of 256 columns
 KMS = (1, 3, 12, 33, 79)
 # 1, 2 hPa: above the first layer mean; 1000 hPa: below the last one on the high ground; the rest inside
 LEVELS = tuple(DI.PLEVS[[0, 1, 10, 18, 25, 30]])
-
-
-def cc(bd, a):
-    return bd.view(a, "A", bd.is_, bd.ie, bd.js, bd.je)
-
-
-def bits_equal(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
 
 
 class Slab:
@@ -92,9 +84,8 @@ GOLDEN_CASES = {"21x7x12": (21, 7, 12, 101), "40x19x33": (40, 19, 33, 102), "21x
                 "33x9x79": (33, 9, 79, 105)}
 
 
-@functools.lru_cache(maxsize=None)
 def golden():
-    return dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "diag_interpolate_vertical.npz")))
+    return H.golden("diag_", "interpolate_vertical")
 
 
 def golden_case(name):
@@ -118,11 +109,8 @@ def check_restatement_against_golden(name):
 def check_lib_against_golden(lib, name, in_ng):
     """the library against the recorded outputs with nothing in between"""
     bd, st, km, ref = golden_case(name)
-    ctx = Context(P.make_grid(bd, False), km, lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, km) as ctx:
         got = run_lib(ctx, bd, st, km, in_ng, out_fill="pattern")
-    finally:
-        ctx.close()
     for n in ref:
         assert bits_equal(got[n], ref[n]), f"{name}: {n} is not the compiled reference's, max diff {np.max(np.abs(got[n] - ref[n])):.3e}"
 
@@ -134,11 +122,8 @@ def check_on_a_layer_mean(lib):
     pm = 0.5 * (st["peln"][:, :-1, :] + st["peln"][:, 1:, :])
     levels = tuple(float(np.exp(pm[3, k, 2])) for k in (0, 4, km - 1))
     ref = run_ref(bd, st, km, levels)
-    ctx = Context(P.make_grid(bd, False), km, lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, km) as ctx:
         got = run_lib(ctx, bd, st, km, 3, levels=levels)
-    finally:
-        ctx.close()
     for n in ref:
         assert bits_equal(got[n], ref[n]), n
 
@@ -146,20 +131,12 @@ def check_on_a_layer_mean(lib):
 def check_refusals(lib):
     nx, ny, km = 12, 9, 12
     bd, st = DI.columns(nx, ny, km, seed=3)
-    ctx = Context(P.make_grid(bd, False), km, lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, km) as ctx:
         peln, a3 = ctx.from_host(st["peln"]), ctx.from_host(st["pt"])
         pat = host_out((nx, ny), "pattern")
         a2 = ctx.from_host(pat)
-
-        def refused(match, *a, **k):
-            try:
-                ctx.interpolate_vertical(*a, **k)
-            except Fv3Error as e:
-                assert match in str(e), (match, str(e))
-            else:
-                raise AssertionError(f"fv3_interpolate_vertical took a call that must be refused ({match})")
-
+        check = H.refusals()
+        refused = lambda match, *a, **k: check(match, call=lambda: ctx.interpolate_vertical(*a, **k))      # noqa: E731
         refused("null", km, 5.0e4, None, a3, a2, in_ng=3)
         refused("null", km, 5.0e4, peln, None, a2, in_ng=3)
         refused("null", km, 5.0e4, peln, a3, None, in_ng=3)
@@ -169,8 +146,6 @@ def check_refusals(lib):
         for ng in (1, 2, -3, 4):
             refused("in_ng", km, 5.0e4, peln, a3, a2, in_ng=ng)
         assert bits_equal(a2.download(), pat), "a refused call wrote"
-    finally:
-        ctx.close()
 
 
 def check_memory_contract(lib, monkeypatch):
@@ -189,13 +164,10 @@ def check_memory_contract(lib, monkeypatch):
         other = MC._tp_case(bd, g, km, 10, 2, 0.06)
         outs = []
         for first in (True, False):
-            ctx = Context(g, km, lib=lib)
-            try:
+            with H.own_or_borrowed(lib, bd, km, grid=g) as ctx:
                 if first:
                     other(ctx)
                 outs.append(run_lib(ctx, bd, st, km, 3, out_fill="pattern"))
-            finally:
-                ctx.close()
         for n in outs[0]:
             assert bits_equal(outs[0][n], outs[1][n]), f"{n} after fv_tp_2d in the same context differs from a fresh context's"
 
@@ -210,11 +182,8 @@ def check_six_faces(lib, npx=13, km=12):
     bd = gs[0].bd
     alone = []
     for t in range(6):
-        ctx = Context(gs[t], km, lib=lib)
-        try:
+        with H.own_or_borrowed(lib, bd, km, grid=gs[t]) as ctx:
             alone.append(run_lib(ctx, bd, sts[t], km, 3, levels=LEVELS[2:4]))
-        finally:
-            ctx.close()
         ref = run_ref(bd, sts[t], km, LEVELS[2:4])
         for name in ref:
             assert bits_equal(alone[t][name], ref[name]), (t, name)
@@ -224,14 +193,12 @@ def check_six_faces(lib, npx=13, km=12):
         peln = mctx.from_host([st["peln"] for st in sts])
         T, vort = mctx.from_host([st["pt"] for st in sts]), mctx.from_host([st["vort"] for st in sts])
         o = {name: [mctx.from_host(np.zeros((n, n), order="F")) for _ in range(2)] for name in ("t", "vort")}
-        mctx.flush()
-        mctx.group.stats()
-        for k, p in enumerate(LEVELS[2:4]):
-            mctx.interpolate_vertical(km, p, peln, T, o["t"][k], in_ng=3)
-            mctx.interpolate_vertical(km, p, peln, vort, o["vort"][k], in_ng=0)
-        mctx.flush()
-        merged, single = mctx.group.stats()
-        assert merged == 4 and single == 0, f"four calls on six faces: {merged} merged launches, {single} single ones"
+
+        def calls():
+            for k, p in enumerate(LEVELS[2:4]):
+                mctx.interpolate_vertical(km, p, peln, T, o["t"][k], in_ng=3)
+                mctx.interpolate_vertical(km, p, peln, vort, o["vort"][k], in_ng=0)
+        H.merged_once(mctx, "four calls", calls, merged=4)      # only here: one output plane per call, so four calls
         for name in o:
             for k in range(2):
                 got = o[name][k].download()

@@ -11,16 +11,16 @@ bit-identical is asserted bit-identical."""
 from __future__ import annotations
 
 import functools
-import os
 
 import numpy as np
 
 import held_suarez_inputs as HI
 import parity_common as P
+import parity_phys as H
 import ref_held_suarez as R
-from gfdl_atmos_cubed_sphere_amd.lib import Context, Fv3Error
+from gfdl_atmos_cubed_sphere_amd.lib import Context
+from parity_phys import compute, same_bits  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SHAPES = ((21, 7, 1), (21, 7, 2), (40, 19, 12), (130, 100, 32))
 IDS = ["21x7x1", "21x7x2", "40x19x12", "130x100x32"]
 DEVICE = HI.DEVICE
@@ -30,9 +30,7 @@ BOUND = {n: 10.0 * v[0] for n, v in MEASURED.items()}
 assert max(BOUND.values()) <= 1.0e-12
 
 
-@functools.lru_cache(maxsize=None)
-def golden(group):
-    return dict(np.load(os.path.join(HERE, "golden", f"held_suarez_{group}.npz")))
+golden = functools.partial(H.golden, "held_suarez_")
 
 
 def params_of(c):
@@ -50,37 +48,26 @@ def call_lib(ctx, d, pr, fresh=False):
 
 
 def upload(ctx, st):
-    return {n: ctx.from_host(st[n]) for n in DEVICE}
+    return H.upload(ctx, st, DEVICE)
 
 
 def download(d):
-    return {n: d[n].download() for n in DEVICE}
+    return H.download(d, DEVICE)
 
 
 def run_lib(lib, bd, st, pr, fresh=False, ctx=None):
     """fv3_held_suarez_tend on a copy of the state -> {field: whole array}"""
-    km = st["pt"].shape[2]
-    own = ctx is None
-    if own:
-        ctx = Context(P.make_grid(bd, False), km, lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, st["pt"].shape[2], ctx) as ctx:
         ctx.upload_lat(st["lat"])
         d = upload(ctx, st)
         call_lib(ctx, d, pr, fresh)
         return download(d)
-    finally:
-        if own:
-            ctx.close()
 
 
 def run_checker(bd, st, pr, teq_out=None):
     o = {n: st[n].copy(order="F") for n in st}
     cnt = R.held_suarez_tend(bd, st["pt"].shape[2], pr, o, teq_out=teq_out)
     return o, cnt
-
-
-def compute(bd, a):
-    return bd.view(a, "A", bd.is_, bd.ie, bd.js, bd.je)
 
 
 def branch_masks(bd, km, pr, st):
@@ -95,21 +82,15 @@ def compare(bd, st, got, ref, pr):
     -> {branch set: relative RMS}"""
     km = st["pt"].shape[2]
     for n in HI.IN:
-        assert np.array_equal(got[n].view(np.uint64), st[n].view(np.uint64)), f"{n}: an input was written"
+        assert same_bits(got[n], st[n]), f"{n}: an input was written"
     for n in ("u_dt", "v_dt"):
-        assert np.array_equal(got[n].view(np.uint64), ref[n].view(np.uint64)), \
+        assert same_bits(got[n], ref[n]), \
             f"{n}: not bit-identical, max diff {np.max(np.abs(got[n] - ref[n])):.3e}"
     out = {}
     for bs, m in branch_masks(bd, km, pr, st).items():
         if not m.any():
             continue
-        a, b = got["t_dt"][m], ref["t_dt"][m]
-        assert np.all(np.isfinite(a)), f"t_dt ({bs}): non-finite values"
-        if BOUND[bs] == 0.0:
-            assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), f"t_dt ({bs}): not bit-identical, max diff {np.max(np.abs(a - b)):.3e}"
-            out[bs] = 0.0
-        else:
-            out[bs] = P.assert_close(f"t_dt ({bs})", a, b, BOUND[bs])
+        out[bs] = H.assert_bounded(f"t_dt ({bs})", got["t_dt"][m], ref["t_dt"][m], BOUND[bs])      # per branch set: each has its own bound
     return out
 
 
@@ -135,7 +116,7 @@ def check_checker_against_golden(name):
     if c["strat"] and c["km"] >= 12:
         assert cnt["meso"] > 0 and cnt["strat"] > 0 and cnt["tropo"] > 0, cnt
     for n in ("u_dt", "v_dt"):
-        assert np.array_equal(got[n].view(np.uint64), ref[n].view(np.uint64)), f"{name}: {n} of the restatement is not the reference's"
+        assert same_bits(got[n], ref[n]), f"{name}: {n} of the restatement is not the reference's"
     for bs, m in branch_masks(bd, c["km"], pr, st).items():
         if m.any():
             P.assert_close(f"{name} t_dt ({bs})", got["t_dt"][m], ref["t_dt"][m], max(BOUND[bs], 10.0 * np.finfo(float).eps))
@@ -156,9 +137,9 @@ def check_lib_against_golden(lib, name):
         import memory_contract as MC
         st2 = dict(st, **{n: MC.pattern_array(st[n].shape) for n in HI.OUT})
         got2 = run_lib(lib, bd, st2, pr, fresh=True)
-        assert np.array_equal(got2["t_dt"].view(np.uint64), got["t_dt"].view(np.uint64)), "t_dt with fresh"
+        assert same_bits(got2["t_dt"], got["t_dt"]), "t_dt with fresh"
         for n in ("u_dt", "v_dt"):
-            assert np.array_equal(compute(bd, got2[n]).view(np.uint64), compute(bd, got[n]).view(np.uint64)), f"{n} with fresh"
+            assert same_bits(compute(bd, got2[n]), compute(bd, got[n])), f"{n} with fresh"
     return out
 
 
@@ -193,15 +174,14 @@ def check_fresh(lib, shape, set_name):
     zeroed = run_lib(lib, bd, st, pr)
     pat = {n: MC.pattern_array(st[n].shape) for n in HI.OUT}
     got = run_lib(lib, bd, dict(st, **pat), pr, fresh=True)
-    assert np.array_equal(got["t_dt"].view(np.uint64), zeroed["t_dt"].view(np.uint64)), "t_dt: fresh differs from zero-then-call"
+    assert same_bits(got["t_dt"], zeroed["t_dt"]), "t_dt: fresh differs from zero-then-call"
     assert np.any(np.signbit(zeroed["t_dt"])) and np.any(zeroed["t_dt"] != 0.0)
     for n in ("u_dt", "v_dt"):
         a, b = compute(bd, got[n]), compute(bd, zeroed[n])
-        assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), f"{n}: fresh differs from zero-then-call"
+        assert same_bits(a, b), f"{n}: fresh differs from zero-then-call"
         assert np.any(b != 0.0) and np.any(b == 0.0), f"{n}: the case has no cell with / without friction"
-        halo = np.ones(got[n].shape, dtype=bool)
-        compute(bd, halo)[...] = False
-        assert np.array_equal(got[n][halo].view(np.uint64), pat[n][halo].view(np.uint64)), f"{n}: fresh wrote the halo"
+        halo = H.halo_mask(bd, got[n].shape)
+        assert same_bits(got[n][halo], pat[n][halo]), f"{n}: fresh wrote the halo"
     for n in HI.OUT:
         a = got[n] if n == "t_dt" else compute(bd, got[n])
         assert np.all(np.abs(a) < 1.0e29), f"{n}: the pattern survives on the compute domain"
@@ -256,23 +236,17 @@ def check_friction_bits(lib, shape, set_name):
     got = run_lib(lib, bd, st, pr)
     for n in ("u_dt", "v_dt"):
         a, b = compute(bd, got[n]), compute(bd, st[n])
-        assert np.array_equal(a[~m].view(np.uint64), b[~m].view(np.uint64)), f"{n}: written where no friction acts"
+        assert same_bits(a[~m], b[~m]), f"{n}: written where no friction acts"
         assert np.all(a[m] != b[m]), f"{n}: unchanged where the friction acts"
 
 
 # ---- age_of_air --------------------------------------------------------------------------------------------------------------------
 def run_age(lib, bd, st, c, ctx=None):
-    own = ctx is None
-    if own:
-        ctx = Context(P.make_grid(bd, False), c["km"], lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, c["km"], ctx) as ctx:
         pe, q = ctx.from_host(st["pe"]), ctx.from_host(st["q"])
         ctx.age_of_air(c["km"], c["time"], pe, q)
-        assert np.array_equal(pe.download().view(np.uint64), st["pe"].view(np.uint64)), "pe was written"
+        assert same_bits(pe.download(), st["pe"]), "pe was written"
         return q.download()
-    finally:
-        if own:
-            ctx.close()
 
 
 def check_age_against_golden(lib, name):
@@ -284,10 +258,10 @@ def check_age_against_golden(lib, name):
     compute(bd, ref)[...] = g[f"{name}|out|q"]
     chk = st["q"].copy(order="F")
     R.age_of_air(bd, c["km"], c["time"], st["pe"], chk)
-    assert np.array_equal(chk.view(np.uint64), ref.view(np.uint64)), f"{name}: the restatement is not the reference's"
+    assert same_bits(chk, ref), f"{name}: the restatement is not the reference's"
     if lib is not None:
         got = run_age(lib, bd, st, c)
-        assert np.array_equal(got.view(np.uint64), ref.view(np.uint64)), f"{name}: q is not the reference's (the halo included)"
+        assert same_bits(got, ref), f"{name}: q is not the reference's (the halo included)"
 
 
 def check_age_against_checker(lib, shape, time):
@@ -297,7 +271,7 @@ def check_age_against_checker(lib, shape, time):
     ref = st["q"].copy(order="F")
     R.age_of_air(bd, km, time, st["pe"], ref)
     got = run_age(lib, bd, st, dict(km=km, time=time))
-    assert np.array_equal(got.view(np.uint64), ref.view(np.uint64))
+    assert same_bits(got, ref)
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------------
@@ -306,14 +280,7 @@ def check_refusals(lib):
     ctx = Context(P.make_grid(bd, False), 12, lib=lib)
     try:
         d = upload(ctx, st)
-
-        def refused(match, p=pr, drop=()):
-            try:
-                call_lib(ctx, dict(d, **{n: None for n in drop}), p)
-            except Fv3Error as e:
-                assert match in str(e), (match, str(e))
-            else:
-                raise AssertionError(f"fv3_held_suarez_tend took a call that must be refused ({match})")
+        refused = H.refusals(functools.partial(call_lib, ctx), d, pr)
 
         ctx.lat_ready = True                     # (the wrapper would upload the gridstruct's on first use)
         refused("no latitude table")
@@ -326,22 +293,10 @@ def check_refusals(lib):
         refused("rd_zur", dict(pr, rd_zur=0.0))
         refused("rd_zur", dict(pr, rd_zur=-1.0))
         refused("radius", dict(pr, radius=0.0))
-        for bad in (dict(pe=None), dict(q=None)):
-            try:
-                ctx.age_of_air(12, 1.0, bad.get("pe", d["pe"]), bad.get("q", d["pt"]))
-            except Fv3Error as e:
-                assert "null" in str(e)
-            else:
-                raise AssertionError("fv3_age_of_air took a null field")
-        try:
-            ctx.age_of_air(0, 1.0, d["pe"], d["pt"])
-        except Fv3Error as e:
-            assert "km" in str(e)
-        else:
-            raise AssertionError("fv3_age_of_air took km = 0")
-        got = download(d)
-        for n in DEVICE:
-            assert np.array_equal(got[n].view(np.uint64), st[n].view(np.uint64)), f"{n}: a refused call wrote"
+        refused("null", call=lambda: ctx.age_of_air(12, 1.0, None, d["pt"]))
+        refused("null", call=lambda: ctx.age_of_air(12, 1.0, d["pe"], None))
+        refused("km", call=lambda: ctx.age_of_air(0, 1.0, d["pe"], d["pt"]))
+        H.assert_nothing_written(d, st, DEVICE)
         # npz < 1 cannot be reached: fv3_create refuses such a domain.  NOT refused: pkz left out with zurita
         call_lib(ctx, dict(d, pkz=None), pr)
     finally:
@@ -352,7 +307,6 @@ def check_refusals(lib):
 def check_six_faces(lib, set_name, npx=13, npz=12):
     """the six faces as one fv3_group: the bits of six single launches, and ONE merged launch"""
     import cubed_common as CC
-    from gfdl_atmos_cubed_sphere_amd.cubed_dyn import MultiContext
     cs, gs = CC.sphere(npx)
     n = npx - 1
     sts = []
@@ -360,26 +314,12 @@ def check_six_faces(lib, set_name, npx=13, npz=12):
         pr, bd, st = generic_case((n, n, npz), set_name, seed=2301 + t)
         sts.append(st)
     alone = [run_lib(lib, bd, st, pr, fresh=bool(t % 2)) for t, st in enumerate(sts)]
-    for fresh in (False, True):
-        mctx = MultiContext([Context(g, npz, lib=lib) for g in gs], group=True)
-        try:
-            assert mctx.group is not None
-            for c, st in zip(mctx.ctxs, sts):
-                c.upload_lat(st["lat"])
-            d = {name: mctx.from_host([st[name] for st in sts]) for name in DEVICE}
-            mctx.flush()
-            mctx.group.stats()
-            call_lib(mctx, d, pr, fresh)
-            mctx.flush()
-            merged, single = mctx.group.stats()
-            assert merged == 1 and single == 0, f"held_suarez_tend of six faces: {merged} merged launches, {single} single ones"
-            for name in DEVICE:
-                got = d[name].download()
-                for t in range(6):
-                    if bool(t % 2) == fresh:
-                        assert np.array_equal(got[t].view(np.uint64), alone[t][name].view(np.uint64)), f"face {t + 1} {name}"
-        finally:
-            mctx.close()
+    def prepare(mctx):
+        for c, st in zip(mctx.ctxs, sts):
+            c.upload_lat(st["lat"])
+    for fresh in (False, True):      # fresh is one flag of the group's call: the faces run alone with it are compared
+        H.six_faces(lib, gs, npz, sts, DEVICE, lambda mctx, d: call_lib(mctx, d, pr, fresh), alone, prepare, "held_suarez_tend",
+                    faces=[t for t in range(6) if bool(t % 2) == fresh])
 
 
 # ---- the memory contract -----------------------------------------------------------------------------------------------------------
@@ -404,16 +344,15 @@ def check_contract(lib, shape, set_name):
         UP.call_lib(ctx, ud, upr)
         q_dt = ud["q_dt"].download()
         again = run_lib(lib, bd, st, pr, ctx=ctx)
-        assert np.array_equal(ud["q_dt"].download().view(np.uint64), q_dt.view(np.uint64)), "q_dt was written"
+        assert same_bits(ud["q_dt"].download(), q_dt), "q_dt was written"
         age = np.asfortranarray(np.random.default_rng(2404).uniform(-1.0, 1.0, bd.shape("A", km)))
         ref_age = age.copy(order="F")
         R.age_of_air(bd, km, 86400.0, st["pe"], ref_age)
         got_age = run_age(lib, bd, dict(pe=st["pe"], q=age), dict(km=km, time=86400.0), ctx=ctx)
-        assert np.array_equal(got_age.view(np.uint64), ref_age.view(np.uint64)), "age_of_air"
+        assert same_bits(got_age, ref_age), "age_of_air"
     finally:
         ctx.close()
-    for n in DEVICE:
-        assert np.array_equal(again[n].view(np.uint64), first[n].view(np.uint64)), f"{n}: a call after fv3_fv_update_phys differs from a fresh context"
+    H.same_as_fresh_context(DEVICE, first, again, "fv3_fv_update_phys")
     return max(worst.values())
 
 
@@ -423,79 +362,30 @@ def check_host(lib, where, set_name="strat", age_tracer=7, time_total=3600.0):
     tile, C12 L8, moist, nq = 7, nonhydrostatic) against restatement-then-fv_update_phys: the restatement of Held_Suarez_Tend on
     zeroed tendencies, the restatement of the column routine of fv_update_phys, a real exchange of u_dt, v_dt and the restatement
     of update_dwinds_phys; the age tracer against age_of_air's restatement on the pe fv_update_phys leaves"""
-    import gfdl_atmos_cubed_sphere_amd.fv_dynamics as M
-    import parity_negadj as NA
-    import parity_remap as PR
-    import parity_subgrid as PS
     import parity_update_phys as UP
-    import ref_fv_sg as SG
-    import ref_update_phys as RU
-    import update_phys_inputs as UI
-    from gfdl_atmos_cubed_sphere_amd.layout import periodic_fill
-    orig, kept = M.FvDynamics, {}
     fields = ("u", "v", "w", "delp", "pt", "ua", "va", "q", "delz", "pe", "peln", "pk", "ps", "pkz")
     strat, zurita = HI.SETS[set_name]
-
-    class HsFvDynamics(orig):
-        def __init__(self, *a, **kw):
-            super().__init__(*a, **kw)
-            if where == "sphere":      # the tests' gridstructs are the oracle's: what update_dwinds_phys reads comes from there as well
-                import cubed_common as CC
-                cs, _ = CC.sphere(self.ctx.grid.npx)
-                for t, c in enumerate(self.ctx.ctxs):
-                    c.upload_dwinds(PS.oracle_dwinds_geom(cs, t))
-
-        def step_from_temperature(self, bdt):
-            super().step_from_temperature(bdt)
-            d = self.dc.d
-            dl = lambda n: NA._faces(d[n].download())      # noqa: E731
-            before = {n: [a.copy(order="F") for a in dl(n)] for n in fields}
-            self.held_suarez(bdt, strat=strat, zurita=zurita, age_tracer=age_tracer, time_total=time_total)
-            kept.update(before=before, bdt=bdt, consts=dict(self.neg_adj_consts, kappa=self.fl.akap), ptop=self.fl.ptop, radius=self.radius,
-                        after={n: dl(n) for n in fields + ("u_srf", "v_srf", "t_dt")}, ak=self.ak, bk=self.bk,
-                        lats=[np.asarray(c.grid.m["agrid"])[..., 1] for c in (self.ctx.ctxs if hasattr(self.ctx, "ctxs") else [self.ctx])])
-
-    M.FvDynamics = HsFvDynamics
-    try:
-        base = (NA.run_tile if where == "tile" else NA.run_sphere)(lib)
-    finally:
-        M.FvDynamics = orig
+    base, kept = H.host_step(lib, where, fields, ("u_srf", "v_srf", "t_dt"),
+                             lambda fv, bdt: fv.held_suarez(bdt, strat=strat, zurita=zurita, age_tracer=age_tracer, time_total=time_total))
     bd = base["bd"]
     before, after = kept["before"], kept["after"]
     nf = len(before["pt"])
     npz = before["pt"][0].shape[2]
-    sp = {n: PR.MOIST6[n] for n in UI.SPECIES if n != "sphum"}
-    sp["sphum"] = 1
-    nq = before["q"][0].shape[3]
-    upr = dict(dt=kept["bdt"], ptop=kept["ptop"], hydrostatic=False, phys_hydrostatic=True, gfs_phys=False, nq=nq, ncnst=nq, nwat=PR.MOIST6["nwat"],
-               species=sp, adjust_mass=np.ones(nq, dtype=np.int32), has_qdt=False, tau_h2o=0.0, ak=kept["ak"], bk=kept["bk"])
+    upr = H.update_phys_params(kept, before["q"][0].shape[3], hydrostatic=False, has_qdt=False)
     hpr = dict(pdt=kept["bdt"], strat=strat, zurita=zurita, rd_zur=1.0 / 25.0, radius=kept["radius"], pi=HI.PI)
     r = (bd.is_, bd.ie, bd.js, bd.je)
     ref = []
     for t in range(nf):
         s = {n: before[n][t].copy(order="F") for n in fields}
         s.update(t_dt=np.zeros((bd.nx, bd.ny, npz), order="F"), u_dt=bd.zeros("A", npz), v_dt=bd.zeros("A", npz),
-                 lat=np.asfortranarray(bd.view(kept["lats"][t], "A", *r)))
+                 lat=np.asfortranarray(compute(bd, kept["agrids"][t][..., 1])))
         cnt = R.held_suarez_tend(bd, npz, hpr, s)
         assert cnt["friction"] > 0 and cnt["no_friction"] > 0, cnt
         P.assert_close(f"face {t + 1} t_dt", after["t_dt"][t], s["t_dt"], max(BOUND.values()) or 10.0 * np.finfo(float).eps)
-        s.update(q_dt=np.zeros((bd.nx, bd.ny, npz, nq), order="F"), qdiag=np.zeros(bd.shape("A", npz) + (0,), order="F"),
-                 u_srf=np.zeros((bd.nx, bd.ny), order="F"), v_srf=np.zeros((bd.nx, bd.ny), order="F"))
-        RU.fv_update_phys(bd, npz, upr, s, consts=kept["consts"])
         ref.append(s)
-    if where == "tile":
-        for n in ("u_dt", "v_dt"):
-            periodic_fill(bd, ref[0][n], "A")
-        geoms = [None]
-    else:
-        import cubed_common as CC
-        cs, _ = CC.sphere(base["gs"][0].npx)
-        CC.exchange(cs, ref, ("u_dt", "v_dt"), "A")
-        geoms = [PS.oracle_dwinds_geom(cs, t) for t in range(6)]
+    H.update_phys_reference(where, base, kept, ref, upr)
     worst = 0.0
     for t in range(nf):
-        g = base["g"] if where == "tile" else base["gs"][t]
-        SG.update_dwinds_phys(bd, g.npx, g.npy, g.grid_type, kept["bdt"], ref[t]["u_dt"], ref[t]["v_dt"], ref[t]["u"], ref[t]["v"], geoms[t])
         if age_tracer:
             qa = np.asfortranarray(ref[t]["q"][..., age_tracer - 1])
             R.age_of_air(bd, npz, time_total, ref[t]["pe"], qa)
@@ -507,7 +397,7 @@ def check_host(lib, where, set_name="strat", age_tracer=7, time_total=3600.0):
             assert np.any(b != bd.view(before[n][t], kind, *rg)), n
             worst = max(worst, P.assert_close(f"face {t + 1} {n}", a, b, P.TOL))
         for n in ("delp", "w"):
-            assert np.array_equal(after[n][t].view(np.uint64), before[n][t].view(np.uint64)), f"{n}: the forcing has no such tendency"
+            assert same_bits(after[n][t], before[n][t]), f"{n}: the forcing has no such tendency"
         P.assert_close(f"face {t + 1} delz", after["delz"][t], ref[t]["delz"], P.TOL)
         P.assert_close(f"face {t + 1} pe", after["pe"][t][1:-1, :, 1:-1], ref[t]["pe"][1:-1, :, 1:-1], P.TOL)
         for n in ("peln", "pk"):
@@ -534,28 +424,14 @@ def check_chain(lib):
     ctx = Context(P.make_grid(bd, False), km, lib=lib)
     try:
         fv = FvDynamics(ctx, fl, ak, bk, nq=nq, radius=c["radius"])
-        d = fv.dc.d
-        for n in ("u", "v", "w", "delp", "pt", "ua", "va", "q", "ps", "pe", "peln", "pk", "pkz"):
-            if n in d:
-                d[n].upload(st[n])
-            else:
-                d[n] = ctx.from_host(st[n])
+        d = H.lay_state(fv, ctx, st, ("u", "v", "w", "delp", "pt", "ua", "va", "q", "ps", "pe", "peln", "pk", "pkz"))
         ctx.upload_lat(st["lat"])
         fv.held_suarez(c["pdt"], strat=c["strat"], zurita=c["zurita"], rd_zur=c["rd_zur"])
         got = {n: d[n].download() for n in HI.CHAIN_OUT + ("delp", "q")}
     finally:
         ctx.close()
-
-    def rng(n, a):
-        if n == "u":
-            return bd.view(a, "U", bd.is_, bd.ie, bd.js, bd.je + 1)
-        if n == "v":
-            return bd.view(a, "V", bd.is_, bd.ie + 1, bd.js, bd.je)
-        if n == "pe":
-            return a[1:-1, :, 1:-1]
-        return compute(bd, a) if n in ("pt", "ua", "va", "ps") else a
     for n in HI.CHAIN_OUT:
-        a, b = rng(n, got[n]), g[f"chain|out|{n}"]
+        a, b = H.written_range(bd, n, got[n], ("pt", "ua", "va", "ps")), g[f"chain|out|{n}"]
         if n == "t_dt":
             pr = params_of(dict(c))
             for bs, m in branch_masks(bd, km, pr, st).items():
@@ -566,6 +442,6 @@ def check_chain(lib):
         elif n in UP.BOUND:
             P.assert_close(f"chain {n}", a, b, UP.BOUND[n])
         else:
-            assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), f"chain: {n} is not the reference's, max diff {np.max(np.abs(a - b)):.3e}"
+            assert same_bits(a, b), f"chain: {n} is not the reference's, max diff {np.max(np.abs(a - b)):.3e}"
     for n in ("delp", "q"):      # the reference's q_dt is zero there: the air mass and the tracers keep their bits
-        assert np.array_equal(got[n].view(np.uint64), st[n].view(np.uint64)), n
+        assert same_bits(got[n], st[n]), n

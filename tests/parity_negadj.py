@@ -7,9 +7,10 @@ from __future__ import annotations
 import numpy as np
 
 import parity_common as P
+import parity_phys as H
 import ref_neg_adj3 as R
 from gfdl_atmos_cubed_sphere_amd.layout import Bounds
-from gfdl_atmos_cubed_sphere_amd.lib import Context, Fv3Error
+from gfdl_atmos_cubed_sphere_amd.lib import Context
 
 SPECIES = ("qv", "ql", "qr", "qi", "qs", "qg")     # tracer order sphum, liq_wat, rainwat, ice_wat, snowwat, graupel (+ cld_amt)
 FIELDS = ("pt",) + SPECIES + ("qa",)
@@ -144,11 +145,7 @@ def tracer_array(st, with_qa):
 
 def run_lib(lib, bd, st, hydrostatic, with_qa, ctx=None, grid=None):
     """fv3_neg_adj3 on a copy of the state -> {field: array with halos}"""
-    npz = st["pt"].shape[2]
-    own = ctx is None
-    if own:
-        ctx = Context(grid if grid is not None else P.make_grid(bd, False), npz, lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, st["pt"].shape[2], ctx, grid) as ctx:
         d_pt, d_dp, d_q = ctx.from_host(st["pt"]), ctx.from_host(st["delp"]), ctx.from_host(tracer_array(st, with_qa))
         d_dz = None if hydrostatic else ctx.from_host(st["delz"])
         d_pl = ctx.from_host(st["peln"]) if hydrostatic else None
@@ -159,9 +156,6 @@ def run_lib(lib, bd, st, hydrostatic, with_qa, ctx=None, grid=None):
             got[s] = q[:, :, :, n]
         assert np.array_equal(d_dp.download(), st["delp"])
         return got
-    finally:
-        if own:
-            ctx.close()
 
 
 def assert_every_branch(cnt, with_qa):
@@ -178,8 +172,7 @@ def compare(bd, st, got, ref):
         worst = max(worst, P.assert_close(n, g, f, P.TOL))
         same = f == s
         assert np.array_equal(g[same], s[same]), f"{n}: a cell the reference leaves unchanged came back different"
-        halo = np.ones(st[n].shape, dtype=bool)
-        bd.view(halo, "A", *r)[...] = False
+        halo = H.halo_mask(bd, st[n].shape)
         assert np.array_equal(got[n][halo], st[n][halo]), f"{n}: the halo was written"
     return worst
 
@@ -242,13 +235,9 @@ def check_refusals(lib):
     ctx = Context(P.make_grid(bd, False), 4, lib=lib)
     try:
         d_pt, d_dp, d_q = ctx.from_host(st["pt"]), ctx.from_host(st["delp"]), ctx.from_host(tracer_array(st, False))
-        for hyd in (False, True):                            # a NULL delz when nonhydrostatic, a NULL peln when hydrostatic
-            try:
-                ctx.neg_adj3(hyd, None, None, d_dp, d_pt, d_q)
-            except Fv3Error as e:
-                assert "delz" in str(e) or "peln" in str(e)
-            else:
-                raise AssertionError("fv3_neg_adj3 took a call without delz / peln")
+        refused = H.refusals()
+        refused("delz", call=lambda: ctx.neg_adj3(False, None, None, d_dp, d_pt, d_q))      # a NULL delz when nonhydrostatic,
+        refused("peln", call=lambda: ctx.neg_adj3(True, None, None, d_dp, d_pt, d_q))       # a NULL peln when hydrostatic
         assert np.array_equal(d_q.download(), tracer_array(st, False))
     finally:
         ctx.close()
@@ -257,7 +246,6 @@ def check_refusals(lib):
 def check_six_faces(lib, npx=13, npz=6, hydrostatic=False):
     """the six faces as one fv3_group (cubed_dyn.MultiContext): the same fields as face by face, and ONE launch for the six"""
     import cubed_common as CC
-    from gfdl_atmos_cubed_sphere_amd.cubed_dyn import MultiContext
     cs, gs = CC.sphere(npx)
     n = npx - 1
     sts = [planted_state(n, n, npz, seed=70 + t, per_case=3) for t in range(6)]
@@ -266,26 +254,12 @@ def check_six_faces(lib, npx=13, npz=6, hydrostatic=False):
     for t, (_, st) in enumerate(sts):
         ref, cnt = reference(bd, st, hydrostatic, True)
         compare(bd, st, alone[t], ref)
-    mctx = MultiContext([Context(g, npz, lib=lib) for g in gs], group=True)
-    try:
-        assert mctx.group is not None
-        up = lambda name: mctx.from_host([st[name] for _, st in sts])
-        d_pt, d_dp, d_q = up("pt"), up("delp"), mctx.from_host([tracer_array(st, True) for _, st in sts])
-        d_dz = None if hydrostatic else up("delz")
-        d_pl = up("peln") if hydrostatic else None
-        mctx.flush()
-        mctx.group.stats()
-        mctx.neg_adj3(hydrostatic, d_pl, d_dz, d_dp, d_pt, d_q, qa=7, consts=R.CONSTS)
-        mctx.flush()
-        merged, single = mctx.group.stats()
-        assert merged == 1 and single == 0, f"neg_adj3 of six faces: {merged} merged launches, {single} single ones"
-        pt, q = d_pt.download(), d_q.download()
-        for t in range(6):
-            assert np.array_equal(pt[t], alone[t]["pt"]), f"face {t + 1} pt"
-            for k, s in enumerate(SPECIES + ("qa",)):
-                assert np.array_equal(q[t][:, :, :, k], alone[t][s]), f"face {t + 1} {s}"
-    finally:
-        mctx.close()
+    # this package hands its tracers as one array: the states and the single runs in that form, the inputs as they went
+    names = ("pt", "delp", "q", "peln" if hydrostatic else "delz")
+    packed = [dict(st, q=tracer_array(st, True)) for _, st in sts]
+    alone = [dict(p, pt=a["pt"], q=tracer_array(a, True)) for p, a in zip(packed, alone)]
+    H.six_faces(lib, gs, npz, packed, names, label="neg_adj3", alone=alone,
+                call=lambda mctx, d: mctx.neg_adj3(hydrostatic, d.get("peln"), d.get("delz"), d["delp"], d["pt"], d["q"], qa=7, consts=R.CONSTS))
 
 
 # ---- the hosts: FvDynamics with the switches of the tail of fv_dynamics ------------------------------------------------------------

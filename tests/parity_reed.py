@@ -17,16 +17,16 @@ LIBRARY below."""
 from __future__ import annotations
 
 import functools
-import os
 
 import numpy as np
 
 import parity_common as P
+import parity_phys as H
 import reed_inputs as RI
 import ref_reed as R
-from gfdl_atmos_cubed_sphere_amd.lib import Context, Fv3Error
+from gfdl_atmos_cubed_sphere_amd.lib import Context
+from parity_phys import compute, same_bits  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 DEVICE = RI.DEVICE
 TEND = ("u_dt", "v_dt", "t_dt", "q_dt")
 # (flag set, field) -> relative RMS, perturbed restatement against the restatement, worst of 8 seeds x the recorded cases
@@ -58,13 +58,7 @@ def fields_of(c):
     return TEND + (("rain",) if c["do_reed_cond"] else ())
 
 
-@functools.lru_cache(maxsize=None)
-def golden(group):
-    return {k.replace("%", "/"): v for k, v in np.load(os.path.join(HERE, "golden", "reed", f"{group}.npz")).items()}
-
-
-def compute(bd, a):
-    return bd.view(a, "A", bd.is_, bd.ie, bd.js, bd.je)
+golden = functools.partial(H.golden, "reed/", slashes=True)
 
 
 def call_lib(ctx, d, pr, fresh=False):
@@ -74,27 +68,20 @@ def call_lib(ctx, d, pr, fresh=False):
 
 
 def upload(ctx, st):
-    return {n: ctx.from_host(st[n]) for n in DEVICE}
+    return H.upload(ctx, st, DEVICE)
 
 
 def download(d):
-    return {n: d[n].download() for n in DEVICE}
+    return H.download(d, DEVICE)
 
 
 def run_lib(lib, bd, st, pr, fresh=False, ctx=None):
     """fv3_reed_sim_phys on a copy of the state -> {field: whole array}"""
-    km = st["pt"].shape[2]
-    own = ctx is None
-    if own:
-        ctx = Context(P.make_grid(bd, False), km, lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, st["pt"].shape[2], ctx) as ctx:
         ctx.grid_upload_reed(pr["reed_test"], st["lat"], consts=pr["consts"])
         d = upload(ctx, st)
         call_lib(ctx, d, pr, fresh)
         return download(d)
-    finally:
-        if own:
-            ctx.close()
 
 
 def run_checker(bd, st, pr, M=None):
@@ -105,46 +92,35 @@ def run_checker(bd, st, pr, M=None):
 
 def lib_planes(lib, lat, test, consts=None):
     bd = RI.Bounds(1, lat.shape[0], 1, lat.shape[1])
-    ctx = Context(P.make_grid(bd, False), 1, lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, 1) as ctx:
         ctx.grid_upload_reed(test, lat, consts=consts or RI.CONSTS)
         return ctx.grid_download_reed()
-    finally:
-        ctx.close()
 
 
 def lib_k1(lib, bd, agrid):
-    ctx = Context(P.make_grid(bd, False), 1, lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, 1) as ctx:
         ctx.grid_upload_terminator(agrid, RI.PI)
         return ctx.grid_download_terminator()
-    finally:
-        ctx.close()
 
 
 def compare(bd, st, got, ref, c, what=""):
     """every input unchanged, the halo of u_dt, v_dt unchanged, each output field at its bound -> {field: relative RMS}"""
     fam = family(c)
     for n in RI.IN:
-        assert np.array_equal(got[n].view(np.uint64), st[n].view(np.uint64)), f"{what}{n}: an input was written"
+        assert same_bits(got[n], st[n]), f"{what}{n}: an input was written"
     for n in ("u_dt", "v_dt"):
-        halo = np.ones(got[n].shape, dtype=bool)
-        compute(bd, halo)[...] = False
-        assert np.array_equal(got[n][halo].view(np.uint64), st[n][halo].view(np.uint64)), f"{what}{n}: the halo was written"
+        halo = H.halo_mask(bd, got[n].shape)
+        assert same_bits(got[n][halo], st[n][halo]), f"{what}{n}: the halo was written"
     if not c["do_reed_cond"]:
-        assert np.array_equal(got["rain"].view(np.uint64), st["rain"].view(np.uint64)), f"{what}rain: written without do_reed_cond"
+        assert same_bits(got["rain"], st["rain"]), f"{what}rain: written without do_reed_cond"
     out = {}
     for n in fields_of(c):
         a, b = (compute(bd, got[n]), compute(bd, ref[n])) if n in ("u_dt", "v_dt") else (got[n], ref[n])
-        assert np.all(np.isfinite(a)), f"{what}{n}: non-finite values"
-        if bound(fam, n) == 0.0:
-            assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), f"{what}{n}: not bit-identical, max diff {np.max(np.abs(a - b)):.3e}"
-            out[n] = 0.0
-        elif not b.any():
-            assert not a.any(), f"{what}{n}: the reference is zero"
+        if bound(fam, n) != 0.0 and not b.any():      # only here: a reference field that is all zero (no relative figure) must come back zero
+            assert np.all(np.isfinite(a)) and not a.any(), f"{what}{n}: the reference is zero"
             out[n] = 0.0
         else:
-            out[n] = P.assert_close(f"{what}{n} ({fam})", a, b, bound(fam, n))
+            out[n] = H.assert_bounded(f"{what}{n} ({fam})", a, b, bound(fam, n))
     return out
 
 
@@ -196,10 +172,10 @@ def check_lib_against_golden(lib, name):
         got2 = run_lib(lib, bd, st2, pr, fresh=True)
         for n in TEND:
             a, b = (compute(bd, got2[n]), compute(bd, got[n])) if n in ("u_dt", "v_dt") else (got2[n], got[n])
-            assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), f"{name}: {n} with fresh differs from zero-then-call"
+            assert same_bits(a, b), f"{name}: {n} with fresh differs from zero-then-call"
             assert np.all(np.abs(a) < 1.0e29), f"{name}: {n}: the pattern survives on the compute domain"
         if c["do_reed_cond"]:
-            assert np.array_equal(got2["rain"].view(np.uint64), got["rain"].view(np.uint64)), f"{name}: rain with fresh"
+            assert same_bits(got2["rain"], got["rain"]), f"{name}: rain with fresh"
     return out
 
 
@@ -207,18 +183,18 @@ def check_planes(lib):
     """the host-formed planes against the same expressions from the reference's compiler, bit for bit, on every recorded latitude"""
     g = golden("planes")
     lat = RI.latitude()
-    assert np.array_equal(g["lat"].view(np.uint64), lat.view(np.uint64))
+    assert same_bits(g["lat"], lat)
     assert 0.5 * RI.PI - lat.max() <= 1.0e-12 and 0.5 * RI.PI + lat.min() <= 1.0e-12
     for test in (0, 1):
         ts, sf = lib_planes(lib, lat, test)
         for n, a in (("tsurf", ts), ("sstf", sf)):
             b = g[f"t{test}|{n}"]
-            assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), \
+            assert same_bits(a, b), \
                 f"reed_test {test} {n}: not the compiler's, max relative difference {np.max(np.abs(a - b) / np.abs(b)):.3e}"
     for name in RI.TERM_CASES:
         bd, st = RI.term_inputs(name)
         a, b = lib_k1(lib, bd, st["agrid"]), g[f"{name}|k1"]
-        assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), f"{name} k1: not the compiler's, max difference {np.max(np.abs(a - b)):.3e}"
+        assert same_bits(a, b), f"{name} k1: not the compiler's, max difference {np.max(np.abs(a - b)):.3e}"
 
 
 # ---- fresh, properties -------------------------------------------------------------------------------------------------------------
@@ -250,13 +226,12 @@ def check_fresh(lib, shape, flags, reed_test=0):
     got = run_lib(lib, bd, dict(st, **pat), pr, fresh=True)
     for n in TEND:
         a, b = (compute(bd, got[n]), compute(bd, zeroed[n])) if n in ("u_dt", "v_dt") else (got[n], zeroed[n])
-        assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), f"{n}: fresh differs from zero-then-call"
+        assert same_bits(a, b), f"{n}: fresh differs from zero-then-call"
         assert np.all(np.abs(a) < 1.0e29), f"{n}: the pattern survives on the compute domain"
     for n in ("u_dt", "v_dt"):
-        halo = np.ones(got[n].shape, dtype=bool)
-        compute(bd, halo)[...] = False
-        assert np.array_equal(got[n][halo].view(np.uint64), pat[n][halo].view(np.uint64)), f"{n}: fresh wrote the halo"
-    assert np.array_equal(got["rain"].view(np.uint64), zeroed["rain"].view(np.uint64))
+        halo = H.halo_mask(bd, got[n].shape)
+        assert same_bits(got[n][halo], pat[n][halo]), f"{n}: fresh wrote the halo"
+    assert same_bits(got["rain"], zeroed["rain"])
 
 
 def check_test2_and_rain(lib, shape):
@@ -268,7 +243,7 @@ def check_test2_and_rain(lib, shape):
         pr = RI.params_of(c)
         got = run_lib(lib, bd, st, pr)
         for n in TEND + RI.IN:
-            assert np.array_equal(got[n].view(np.uint64), st[n].view(np.uint64)), f"{n}: written with reed_test = 2"
+            assert same_bits(got[n], st[n]), f"{n}: written with reed_test = 2"
         st2 = dict(st, **{n: MC.pattern_array(st[n].shape) for n in TEND})
         got2 = run_lib(lib, bd, st2, pr, fresh=True)
         for n in TEND:
@@ -278,35 +253,25 @@ def check_test2_and_rain(lib, shape):
             if c["do_reed_cond"]:
                 assert not g["rain"].any()
             else:
-                assert np.array_equal(g["rain"].view(np.uint64), st["rain"].view(np.uint64)), "rain: written without do_reed_cond"
+                assert same_bits(g["rain"], st["rain"]), "rain: written without do_reed_cond"
     c, bd, st = generic_case(shape, "nocond", reed_test=0, seed=6302)
     got = run_lib(lib, bd, st, RI.params_of(c))
-    assert np.array_equal(got["rain"].view(np.uint64), st["rain"].view(np.uint64)), "rain: written without do_reed_cond"
+    assert same_bits(got["rain"], st["rain"]), "rain: written without do_reed_cond"
     assert not np.array_equal(got["t_dt"], st["t_dt"])
 
 
 # ---- the terminator ----------------------------------------------------------------------------------------------------------------
 def run_term(lib, bd, st, c, ctx=None):
-    own = ctx is None
-    if own:
-        ctx = Context(P.make_grid(bd, False), c["km"], lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, c["km"], ctx) as ctx:
         ctx.grid_upload_terminator(st["agrid"], RI.PI)
         cl, cl2 = ctx.from_host(st["cl"]), ctx.from_host(st["cl2"])
         ctx.terminator_advance(c["km"], c["pdt"], cl, cl2, term_fill_negative=c["fill"])
         return dict(cl=cl.download(), cl2=cl2.download())
-    finally:
-        if own:
-            ctx.close()
 
 
 def term_compare(what, got, ref):
     for n in ("cl", "cl2"):
-        assert np.all(np.isfinite(got[n])), f"{what} {n}"
-        if TERM_MEASURED[n] == 0.0:
-            assert np.array_equal(got[n].view(np.uint64), ref[n].view(np.uint64)), f"{what} {n}"
-        else:
-            P.assert_close(f"{what} {n}", got[n], ref[n], 10.0 * TERM_MEASURED[n])
+        H.assert_bounded(f"{what} {n}", got[n], ref[n], 10.0 * TERM_MEASURED[n])
 
 
 def check_term_against_golden(lib, name):
@@ -350,14 +315,7 @@ def check_refusals(lib):
     ctx = Context(P.make_grid(bd, False), 12, lib=lib)
     try:
         d = upload(ctx, st)
-
-        def refused(match, p=pr, drop=(), call=None):
-            try:
-                (call or (lambda: call_lib(ctx, dict(d, **{n: None for n in drop}), p)))()
-            except Fv3Error as e:
-                assert match in str(e), (match, str(e))
-            else:
-                raise AssertionError(f"a call that must be refused was taken ({match})")
+        refused = H.refusals(functools.partial(call_lib, ctx), d, pr)
 
         ctx.reed_ready = 0                       # (the wrapper would upload the gridstruct's on first use)
         refused("no Reed table")
@@ -382,9 +340,7 @@ def check_refusals(lib):
         refused("same plane", call=lambda: ctx.terminator_advance(12, 225.0, cl, cl))
         refused("km", call=lambda: ctx.terminator_advance(0, 225.0, cl, cl2))
         refused("pdt", call=lambda: ctx.terminator_advance(12, 0.0, cl, cl2))
-        got = download(d)
-        for n in DEVICE:
-            assert np.array_equal(got[n].view(np.uint64), st[n].view(np.uint64)), f"{n}: a refused call wrote"
+        H.assert_nothing_written(d, st, DEVICE)
         assert not cl.download().any() and not cl2.download().any()
         # npz < 1 cannot be reached: fv3_create refuses such a domain.  NOT refused: delz left out when hydrostatic
         call_lib(ctx, dict(d, delz=None), dict(pr, hydrostatic=True))
@@ -396,7 +352,6 @@ def check_refusals(lib):
 def check_six_faces(lib, flags, npx=13, npz=12):
     """the six C12 faces as one fv3_group: the bits of six single launches, and ONE merged launch; the terminator likewise"""
     import cubed_common as CC
-    from gfdl_atmos_cubed_sphere_amd.cubed_dyn import MultiContext
     cs, gs = CC.sphere(npx)
     n = npx - 1
     sts, tsts = [], []
@@ -407,39 +362,21 @@ def check_six_faces(lib, flags, npx=13, npz=12):
     pr = RI.params_of(dict(c, hydrostatic=False))
     alone = [run_lib(lib, bd, st, pr, fresh=bool(t % 2)) for t, st in enumerate(sts)]
     talone = [run_term(lib, bd, st, dict(km=npz, pdt=225.0, fill=True)) for st in tsts]
-    for fresh in (False, True):
-        mctx = MultiContext([Context(g, npz, lib=lib) for g in gs], group=True)
-        try:
-            assert mctx.group is not None
-            for cx, st, tst in zip(mctx.ctxs, sts, tsts):
-                cx.grid_upload_reed(1, st["lat"], consts=pr["consts"])
-                cx.grid_upload_terminator(tst["agrid"], RI.PI)
-            d = {name: mctx.from_host([st[name] for st in sts]) for name in DEVICE}
-            mctx.flush()
-            mctx.group.stats()
-            call_lib(mctx, d, pr, fresh)
-            mctx.flush()
-            merged, single = mctx.group.stats()
-            assert merged == 1 and single == 0, f"reed_sim_phys of six faces: {merged} merged launches, {single} single ones"
-            for name in DEVICE:
-                got = d[name].download()
-                for t in range(6):
-                    if bool(t % 2) == fresh:
-                        assert np.array_equal(got[t].view(np.uint64), alone[t][name].view(np.uint64)), f"face {t + 1} {name}"
-            if not fresh:
-                cl, cl2 = (mctx.from_host([st[name] for st in tsts]) for name in ("cl", "cl2"))
-                mctx.flush()
-                mctx.group.stats()
-                mctx.terminator_advance(npz, 225.0, cl, cl2, term_fill_negative=True)
-                mctx.flush()
-                merged, single = mctx.group.stats()
-                assert merged == 1 and single == 0, f"terminator_advance of six faces: {merged} merged launches, {single} single ones"
-                for name, a in (("cl", cl), ("cl2", cl2)):
-                    got = a.download()
-                    for t in range(6):
-                        assert np.array_equal(got[t].view(np.uint64), talone[t][name].view(np.uint64)), f"face {t + 1} {name}"
-        finally:
-            mctx.close()
+    def prepare(mctx):
+        for cx, st, tst in zip(mctx.ctxs, sts, tsts):
+            cx.grid_upload_reed(1, st["lat"], consts=pr["consts"])
+            cx.grid_upload_terminator(tst["agrid"], RI.PI)
+
+    def terminator(mctx):
+        cl, cl2 = (mctx.from_host([st[name] for st in tsts]) for name in ("cl", "cl2"))
+        H.merged_once(mctx, "terminator_advance", lambda: mctx.terminator_advance(npz, 225.0, cl, cl2, term_fill_negative=True))
+        for name, a in (("cl", cl), ("cl2", cl2)):
+            got = a.download()
+            for t in range(6):
+                assert same_bits(got[t], talone[t][name]), f"face {t + 1} {name}"
+    for fresh in (False, True):      # fresh is one flag of the group's call: the faces run alone with it are compared
+        H.six_faces(lib, gs, npz, sts, DEVICE, lambda mctx, d: call_lib(mctx, d, pr, fresh), alone, prepare, "reed_sim_phys",
+                    faces=[t for t in range(6) if bool(t % 2) == fresh], then=None if fresh else terminator)
 
 
 # ---- the memory contract -----------------------------------------------------------------------------------------------------------
@@ -471,9 +408,8 @@ def check_contract(lib, shape, flags):
         third = run_lib(lib, bd, st, pr, ctx=ctx)
     finally:
         ctx.close()
-    for n in DEVICE:
-        assert np.array_equal(again[n].view(np.uint64), first[n].view(np.uint64)), f"{n}: a call after fv3_fv_update_phys differs from a fresh context"
-        assert np.array_equal(third[n].view(np.uint64), first[n].view(np.uint64)), f"{n}: a call after another branch set differs from a fresh context"
+    H.same_as_fresh_context(DEVICE, first, again, "fv3_fv_update_phys")
+    H.same_as_fresh_context(DEVICE, first, third, "another branch set")
     return max(worst.values())
 
 
@@ -483,56 +419,23 @@ def check_host(lib, where, flags="cond", reed_test=1):
     tile, C12 L8, moist, nq = 7, nonhydrostatic) against restatement-then-fv_update_phys, in the reference's order: the restatement of
     the column loop on zeroed tendencies, the restatement of the terminator on the last two tracers, the restatement of the column
     routine of fv_update_phys with that q_dt, a real exchange of u_dt, v_dt and the restatement of update_dwinds_phys"""
-    import gfdl_atmos_cubed_sphere_amd.fv_dynamics as M
-    import parity_negadj as NA
-    import parity_remap as PR
-    import parity_subgrid as PS
     import parity_update_phys as UP
-    import ref_fv_sg as SG
-    import ref_update_phys as RU
-    import update_phys_inputs as UI
-    from gfdl_atmos_cubed_sphere_amd.layout import periodic_fill
-    orig, kept = M.FvDynamics, {}
     fields = ("u", "v", "w", "delp", "pt", "ua", "va", "q", "delz", "pe", "peln", "pk", "ps", "pkz", "phis")
     cnd, only, alt = RI.FLAGS[flags]
 
-    class ReedFvDynamics(orig):
-        def __init__(self, *a, **kw):
-            super().__init__(*a, **kw)
-            if where == "sphere":      # the tests' gridstructs are the oracle's: what update_dwinds_phys reads comes from there as well
-                import cubed_common as CC
-                cs, _ = CC.sphere(self.ctx.grid.npx)
-                for t, c in enumerate(self.ctx.ctxs):
-                    c.upload_dwinds(PS.oracle_dwinds_geom(cs, t))
+    def call_method(fv, bdt):
+        for c in (fv.ctx.ctxs if hasattr(fv.ctx, "ctxs") else [fv.ctx]):
+            c.grid_upload_reed(reed_test, consts=dict(fv.neg_adj_consts, radius=fv.radius))
+        fv.reed_sim_phys(bdt, reed_test=reed_test, do_reed_cond=cnd, reed_cond_only=only, reed_alt_mxg=alt, terminator=(fv.nq - 1, fv.nq),
+                         term_fill_negative=True)
 
-        def step_from_temperature(self, bdt):
-            super().step_from_temperature(bdt)
-            d = self.dc.d
-            dl = lambda n: NA._faces(d[n].download())      # noqa: E731
-            before = {n: [a.copy(order="F") for a in dl(n)] for n in fields}
-            ctxs = self.ctx.ctxs if hasattr(self.ctx, "ctxs") else [self.ctx]
-            for c in ctxs:
-                c.grid_upload_reed(reed_test, consts=dict(self.neg_adj_consts, radius=self.radius))
-            self.reed_sim_phys(bdt, reed_test=reed_test, do_reed_cond=cnd, reed_cond_only=only, reed_alt_mxg=alt, terminator=(self.nq - 1, self.nq),
-                               term_fill_negative=True)
-            kept.update(before=before, bdt=bdt, consts=dict(self.neg_adj_consts, kappa=self.fl.akap), ptop=self.fl.ptop, radius=self.radius,
-                        after={n: dl(n) for n in fields + ("u_srf", "v_srf", "t_dt", "q_dt", "rain")}, ak=self.ak, bk=self.bk,
-                        agrids=[np.asarray(c.grid.m["agrid"]) for c in ctxs], hyd=self.fl.hydrostatic)
-
-    M.FvDynamics = ReedFvDynamics
-    try:
-        base = (NA.run_tile if where == "tile" else NA.run_sphere)(lib)
-    finally:
-        M.FvDynamics = orig
+    base, kept = H.host_step(lib, where, fields, ("u_srf", "v_srf", "t_dt", "q_dt", "rain"), call_method)
     bd = base["bd"]
     before, after = kept["before"], kept["after"]
     nf = len(before["pt"])
     npz = before["pt"][0].shape[2]
-    sp = {n: PR.MOIST6[n] for n in UI.SPECIES if n != "sphum"}
-    sp["sphum"] = 1
     nq = before["q"][0].shape[3]
-    upr = dict(dt=kept["bdt"], ptop=kept["ptop"], hydrostatic=kept["hyd"], phys_hydrostatic=True, gfs_phys=False, nq=nq, ncnst=nq, nwat=PR.MOIST6["nwat"],
-               species=sp, adjust_mass=np.ones(nq, dtype=np.int32), has_qdt=True, tau_h2o=0.0, ak=kept["ak"], bk=kept["bk"])
+    upr = H.update_phys_params(kept, nq)
     k = dict(RI.CONSTS, **{n: v for n, v in kept["consts"].items() if n in RI.CONSTS}, radius=kept["radius"])
     rpr = dict(pdt=kept["bdt"], hydrostatic=kept["hyd"], reed_test=reed_test, do_reed_cond=cnd, reed_cond_only=only, reed_alt_mxg=alt, consts=k)
     r = (bd.is_, bd.ie, bd.js, bd.je)
@@ -553,23 +456,11 @@ def check_host(lib, where, flags="cond", reed_test=1):
         q4[..., nq - 2], q4[..., nq - 1] = cl, cl2
         qd4 = np.zeros((bd.nx, bd.ny, npz, nq), order="F")
         qd4[..., 0] = s["q_dt"]
-        s.update(q=q4, q_dt=qd4, qdiag=np.zeros(bd.shape("A", npz) + (0,), order="F"), u_srf=np.zeros((bd.nx, bd.ny), order="F"),
-                 v_srf=np.zeros((bd.nx, bd.ny), order="F"))
-        RU.fv_update_phys(bd, npz, upr, s, consts=kept["consts"])
+        s.update(q=q4, q_dt=qd4)
         ref.append(s)
-    if where == "tile":
-        for n in ("u_dt", "v_dt"):
-            periodic_fill(bd, ref[0][n], "A")
-        geoms = [None]
-    else:
-        import cubed_common as CC
-        cs, _ = CC.sphere(base["gs"][0].npx)
-        CC.exchange(cs, ref, ("u_dt", "v_dt"), "A")
-        geoms = [PS.oracle_dwinds_geom(cs, t) for t in range(6)]
+    H.update_phys_reference(where, base, kept, ref, upr)
     worst = 0.0
     for t in range(nf):
-        g = base["g"] if where == "tile" else base["gs"][t]
-        SG.update_dwinds_phys(bd, g.npx, g.npy, g.grid_type, kept["bdt"], ref[t]["u_dt"], ref[t]["v_dt"], ref[t]["u"], ref[t]["v"], geoms[t])
         rows = [("u", "U", (bd.is_, bd.ie, bd.js, bd.je + 1)), ("v", "V", (bd.is_, bd.ie + 1, bd.js, bd.je)), ("pt", "A", r), ("ua", "A", r),
                 ("va", "A", r), ("q", "A", r), ("delp", "A", r)]
         for n, kind, rg in rows:
@@ -605,30 +496,16 @@ def check_chain(lib):
     ctx = Context(P.make_grid(bd, False), km, lib=lib)
     try:
         fv = FvDynamics(ctx, fl, ak, bk, nq=nq, radius=RI.CONSTS["radius"], moist=dict(nwat=1, sphum=1), moist_phys=True)
-        d = fv.dc.d
-        for n in ("u", "v", "w", "delp", "pt", "ua", "va", "q", "ps", "pe", "peln", "pk", "pkz", "phis", "rain"):
-            if n in d:
-                d[n].upload(st[n])
-            else:
-                d[n] = ctx.from_host(st[n])
+        d = H.lay_state(fv, ctx, st, ("u", "v", "w", "delp", "pt", "ua", "va", "q", "ps", "pe", "peln", "pk", "pkz", "phis", "rain"))
         ctx.grid_upload_reed(c["reed_test"], st["lat"], consts=RI.CONSTS)
         fv.reed_sim_phys(c["pdt"], reed_test=c["reed_test"], do_reed_cond=c["do_reed_cond"], reed_cond_only=c["reed_cond_only"],
                          reed_alt_mxg=c["reed_alt_mxg"], consts=RI.CONSTS)
         got = {n: d[n].download() for n in RI.CHAIN_OUT}
     finally:
         ctx.close()
-
-    def rng(n, a):
-        if n == "u":
-            return bd.view(a, "U", bd.is_, bd.ie, bd.js, bd.je + 1)
-        if n == "v":
-            return bd.view(a, "V", bd.is_, bd.ie + 1, bd.js, bd.je)
-        if n == "pe":
-            return a[1:-1, :, 1:-1]
-        return compute(bd, a) if n in ("pt", "ua", "va", "ps", "delp", "q") else a
     fam = family(c)
     for n in RI.CHAIN_OUT:
-        a, b = rng(n, got[n]), g[f"chain|out|{n}"]
+        a, b = H.written_range(bd, n, got[n], ("pt", "ua", "va", "ps", "delp", "q")), g[f"chain|out|{n}"]
         if n in ("t_dt", "q_dt", "rain"):
             a1, b1 = (a[..., 0], b[..., 0]) if n == "q_dt" else (a, b)
             P.assert_close(f"chain {n}", a1, b1, bound(fam, n))

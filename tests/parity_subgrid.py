@@ -7,24 +7,21 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 
 import parity_common as P
+import parity_phys as H
 import ref_fv_sg as R
 import subgrid_inputs as SI
 from gfdl_atmos_cubed_sphere_amd.lib import Context, Fv3Error
+from parity_phys import same_bits
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SHAPES = ((40, 19, 12), (130, 100, 5), (21, 7, 2), (21, 7, 3))
 NWATS = ((0, 1), (1, 1), (2, 2), (3, 4), (4, 4), (6, 7))
 OUT = SI.SG_OUT
-
-
-@functools.lru_cache(maxsize=None)
-def golden(group):
-    return dict(np.load(os.path.join(HERE, "golden", f"subgrid_{group}.npz")))
+IN = ("delp", "pe", "peln", "pkz", "delz")
+golden = functools.partial(H.golden, "subgrid_")
 
 
 def params_of(c):
@@ -51,25 +48,17 @@ def call_lib(ctx, d, pr, species=None):
 
 
 def upload(ctx, st):
-    return {n: ctx.from_host(st[n]) for n in ("delp", "pe", "peln", "pkz", "delz") + OUT}
+    return H.upload(ctx, st, IN + OUT)
 
 
 def run_lib(lib, bd, st, pr, ctx=None, grid=None):
     """fv3_fv_subgrid_z on a copy of the state -> {field: array with halos}; the inputs must come back as they went"""
-    km = st["ta"].shape[2]
-    own = ctx is None
-    if own:
-        ctx = Context(grid if grid is not None else P.make_grid(bd, False), km, lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, st["ta"].shape[2], ctx, grid) as ctx:
         d = upload(ctx, st)
         call_lib(ctx, d, pr)
-        got = {n: d[n].download() for n in OUT}
-        for n in ("delp", "pe", "peln", "pkz", "delz"):
-            assert np.array_equal(d[n].download(), st[n]), f"{n}: an input was written"
-        return got
-    finally:
-        if own:
-            ctx.close()
+        for n in IN:
+            assert same_bits(d[n].download(), st[n]), f"{n}: an input was written"
+        return H.download(d, OUT)
 
 
 def written_mask(bd, st, pr, name):
@@ -109,7 +98,7 @@ def compare(bd, st, got, ref, pr, tol=P.TOL):
         m = written_mask(bd, st, pr, n)
         if m.any():
             worst = max(worst, P.assert_close(n, got[n][m], ref[n][m], tol))
-        assert np.array_equal(got[n][~m].view(np.uint64), st[n][~m].view(np.uint64)), f"{n}: written outside the compute domain / levels 1..kbot / tracers 1..nq"
+        assert same_bits(got[n][~m], st[n][~m]), f"{n}: written outside the compute domain / levels 1..kbot / tracers 1..nq"
     return worst
 
 
@@ -137,7 +126,7 @@ def check_checker_against_golden(name):
     got, cnt = run_checker(bd, st, pr)
     assert_conditions(bd, st, ref, cnt, pr)
     for n in OUT:
-        assert np.array_equal(got[n].view(np.uint64), ref[n].view(np.uint64)), f"{name}: {n} of the restatement is not the reference's, max diff {np.max(np.abs(got[n] - ref[n])):.3e}"
+        assert same_bits(got[n], ref[n]), f"{name}: {n} of the restatement is not the reference's, max diff {np.max(np.abs(got[n] - ref[n])):.3e}"
     if c["ptop"] < 2.0:      # t_min = 160 decides something in this case: with 165 the restatement gives other bits
         other, _ = run_checker(bd, st, dict(pr, ptop=300.0))
         assert not np.array_equal(other["ta"], ref["ta"]), "t_min 160 / 165 makes no difference in the ptop = 1 Pa case"
@@ -207,7 +196,7 @@ def check_properties(lib, shape, hydrostatic, nwat=6, nq=7):
     still = calm & np.all(v(ref["ua"]) == v(st["ua"]), axis=2) & np.all(v(ref["qa"]) == v(st["qa"]), axis=(2, 3))
     assert still.sum() >= calm.sum() // 2 > 0, "the calm columns mix: the test shows nothing"
     for n in ("ua", "va", "qa") + (() if hydrostatic else ("w",)):
-        assert np.array_equal(v(got[n])[still].view(np.uint64), v(st[n])[still].view(np.uint64)), f"{n}: a column without mixing came back different"
+        assert same_bits(v(got[n])[still], v(st[n])[still]), f"{n}: a column without mixing came back different"
     for n in ("u_dt", "v_dt"):
         assert np.all(v(got[n])[still] == 0.0), n
 
@@ -239,8 +228,7 @@ def check_contract(lib, shape=(40, 19, 12), hydrostatic=False):
         again = run_lib(lib, bd, st, pr, ctx=ctx)
     finally:
         ctx.close()
-    for n in OUT:
-        assert np.array_equal(again[n].view(np.uint64), fresh[n].view(np.uint64)), f"{n}: a call after another call differs from a fresh context"
+    H.same_as_fresh_context(OUT, fresh, again, "another call")
     return worst
 
 
@@ -254,15 +242,7 @@ def check_refusals(lib):
     ctx = Context(P.make_grid(bd, False), km, lib=lib)
     try:
         d = upload(ctx, st)
-
-        def refused(match, pr=good, species=None, drop=()):
-            dd = dict(d, **{n: None for n in drop})
-            try:
-                call_lib(ctx, dd, pr, species=species)
-            except Fv3Error as e:
-                assert match in str(e), (match, str(e))
-            else:
-                raise AssertionError(f"fv3_fv_subgrid_z took a call that must be refused ({match})")
+        refused = H.refusals(functools.partial(call_lib, ctx), d, good)
 
         for n in ("delp", "peln", "pkz", "ta", "qa", "ua", "va", "u_dt", "v_dt"):
             refused("null", drop=(n,))
@@ -280,8 +260,7 @@ def check_refusals(lib):
         refused("rainwat", dict(good, nwat=4), species=dict(sphum=1, liq_wat=2))
         refused("snowwat", dict(good, nwat=5), species=dict(sphum=1, liq_wat=2, rainwat=3, ice_wat=4))
         refused("nwat", dict(good, nwat=-1), species=six)
-        for n in OUT:
-            assert np.array_equal(d[n].download(), st[n]), f"{n}: a refused call wrote"
+        H.assert_nothing_written(d, st, IN + OUT)
         # what is NOT refused, and why: k_bot_full > npz with fv_sg_adj_weak > 0 (kbot = npz, fv_sg.F90:123-128); nwat = 5 and 7 with all
         # five condensates (the reference's `else` branches, :242-248, :302-307, :358-361, :436-442: the arithmetic of nwat = 6)
         call_lib(ctx, upload(ctx, st), dict(good, k_bot_full=km + 1, fv_sg_adj_weak=900))
@@ -296,40 +275,24 @@ def check_refusals(lib):
         bdh, sth = SI.columns(nx, ny, km, 1, 0, seed=402)
         sth["u_dt"], sth["v_dt"] = bd.zeros("A", km), bd.zeros("A", km)
         dh = upload(ctx, {k: v for k, v in sth.items() if k != "planted"})
-        try:
-            call_lib(ctx, dict(dh, pe=None), params_of(dict(hydrostatic=True, nwat=0, nq=1, k_bot_full=4)))
-        except Fv3Error as e:
-            assert "pe" in str(e)
-        else:
-            raise AssertionError("a hydrostatic call without pe was taken")
+        refused("pe", call=lambda: call_lib(ctx, dict(dh, pe=None), params_of(dict(hydrostatic=True, nwat=0, nq=1, k_bot_full=4))))
         # update_dwinds_phys: null fields
         t = SI.tile_tendencies(nx, ny, km, seed=5)[1]
         dt_ = {n: ctx.from_host(t[n]) for n in t}
         for n in t:
-            try:
-                ctx.update_dwinds_phys(1.0, *(None if m == n else dt_[m] for m in ("u_dt", "v_dt", "u", "v")))
-            except Fv3Error as e:
-                assert "null" in str(e)
-            else:
-                raise AssertionError("fv3_update_dwinds_phys took a null field")
+            refused("null", call=lambda: ctx.update_dwinds_phys(1.0, *(None if m == n else dt_[m] for m in ("u_dt", "v_dt", "u", "v"))))
     finally:
         ctx.close()
 
 
 # ---- update_dwinds_phys on the doubly periodic tile --------------------------------------------------------------------------------
 def run_dwinds_lib(lib, bd, t, dt, npz, grid=None, ctx=None):
-    own = ctx is None
-    if own:
-        ctx = Context(grid if grid is not None else P.make_grid(bd, False), npz, lib=lib)
-    try:
-        d = {n: ctx.from_host(t[n]) for n in ("u_dt", "v_dt", "u", "v")}
+    with H.own_or_borrowed(lib, bd, npz, ctx, grid) as ctx:
+        d = H.upload(ctx, t, ("u_dt", "v_dt", "u", "v"))
         ctx.update_dwinds_phys(dt, d["u_dt"], d["v_dt"], d["u"], d["v"])
         for n in ("u_dt", "v_dt"):
-            assert np.array_equal(d[n].download(), t[n]), n
+            assert same_bits(d[n].download(), t[n]), n
         return d["u"].download(), d["v"].download()
-    finally:
-        if own:
-            ctx.close()
 
 
 def compare_dwinds(bd, t, u, v, ru, rv):
@@ -340,7 +303,7 @@ def compare_dwinds(bd, t, u, v, ru, rv):
         bd.view(m, kind, *rg)[...] = True
         assert np.any(ref[m] != t[n][m])
         worst = max(worst, P.assert_close(n, got[m], ref[m], P.TOL))
-        assert np.array_equal(got[~m].view(np.uint64), t[n][~m].view(np.uint64)), f"{n}: written outside its range"
+        assert same_bits(got[~m], t[n][~m]), f"{n}: written outside its range"
     return worst
 
 
@@ -361,7 +324,7 @@ def check_dwinds_checker_against_golden(name):
     R.update_dwinds_phys(bd, npx, npy, gt, SI.DW_DT, t["u_dt"], t["v_dt"], u, v, geom)
     assert np.any(ru != t["u"]) and np.any(rv != t["v"])
     for n, a, b in (("u", u, ru), ("v", v, rv)):
-        assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), f"{name}: {n} of the restatement is not the reference's, max diff {np.max(np.abs(a - b)):.3e}"
+        assert same_bits(a, b), f"{name}: {n} of the restatement is not the reference's, max diff {np.max(np.abs(a - b)):.3e}"
 
 
 def check_dwinds_lib_against_golden(lib, name):
@@ -489,7 +452,6 @@ def check_geometry_against_oracle(npx=13, tol=1.0e-11):
 def check_six_faces(lib, npx=13, npz=6, hydrostatic=False):
     """the six faces as one fv3_group: the bits of face-by-face runs, and ONE merged launch for the column kernel"""
     import cubed_common as CC
-    from gfdl_atmos_cubed_sphere_amd.cubed_dyn import MultiContext
     cs, gs = CC.sphere(npx)
     n = npx - 1
     pr = params_of(dict(hydrostatic=hydrostatic, nwat=6, nq=7, k_bot_full=4))
@@ -505,22 +467,8 @@ def check_six_faces(lib, npx=13, npz=6, hydrostatic=False):
         ref, cnt = run_checker(bd, st, pr)
         assert cnt["mixed"][0] > 0 and cnt["not_mixed"][0] > 0
         compare(bd, st, alone[t], ref, pr)
-    mctx = MultiContext([Context(g, npz, lib=lib) for g in gs], group=True)
-    try:
-        assert mctx.group is not None
-        d = {name: mctx.from_host([st[name] for st in sts]) for name in ("delp", "pe", "peln", "pkz", "delz") + OUT}
-        mctx.flush()
-        mctx.group.stats()
-        call_lib(mctx, d, pr)
-        mctx.flush()
-        merged, single = mctx.group.stats()
-        assert merged == 1 and single == 0, f"fv_subgrid_z of six faces: {merged} merged launches, {single} single ones"
-        for name in OUT:
-            got = d[name].download()
-            for t in range(6):
-                assert np.array_equal(got[t].view(np.uint64), alone[t][name].view(np.uint64)), f"face {t + 1} {name}"
-    finally:
-        mctx.close()
+    alone = [dict({n: st[n] for n in IN}, **a) for st, a in zip(sts, alone)]      # the inputs come back as they went
+    H.six_faces(lib, gs, npz, sts, IN + OUT, lambda mctx, d: call_lib(mctx, d, pr), alone, label="fv_subgrid_z")
 
 
 # ---- the Python host: FvDynamics.atmosphere_step ---------------------------------------------------------------------------------

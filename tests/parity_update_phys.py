@@ -13,17 +13,16 @@ pk / (pk(k+1) - pk(k)), about 20 here; pk inherits kappa times the absolute erro
 from __future__ import annotations
 
 import functools
-import os
 
 import numpy as np
 
 import parity_common as P
-import ref_fv_sg as SG
+import parity_phys as H
 import ref_update_phys as R
 import update_phys_inputs as UI
-from gfdl_atmos_cubed_sphere_amd.lib import Context, Fv3Error
+from gfdl_atmos_cubed_sphere_amd.lib import Context
+from parity_phys import same_bits
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SHAPES = ((21, 7, 1), (21, 7, 2), (40, 19, 12), (130, 100, 5))
 NWATS = (0, 1, 2, 3, 4, 5, 6)
 OUT = UI.OUT
@@ -32,9 +31,7 @@ assert max(BOUND.values()) <= 1.0e-12
 DEVICE = ("u_dt", "v_dt", "t_dt", "q_dt", "delp", "pt", "q", "qdiag", "ua", "va", "w", "delz", "ps", "pe", "peln", "pk", "pkz", "u_srf", "v_srf", "u", "v")
 
 
-@functools.lru_cache(maxsize=None)
-def golden(group):
-    return dict(np.load(os.path.join(HERE, "golden", f"update_phys_{group}.npz")))
+golden = functools.partial(H.golden, "update_phys_")
 
 
 def params_of(c):
@@ -62,7 +59,7 @@ def nonempty(a):
 
 
 def upload(ctx, st):
-    return {n: ctx.from_host(nonempty(st[n])) for n in DEVICE}
+    return H.upload(ctx, {n: nonempty(st[n]) for n in DEVICE}, DEVICE)
 
 
 def download(d, st):
@@ -72,20 +69,13 @@ def download(d, st):
 def run_lib(lib, bd, st, pr, ctx=None, grid=None, whole=False):
     """fv3_fv_update_phys on a copy of the state (whole: then the periodic halo update of u_dt, v_dt and fv3_update_dwinds_phys, the
     sequence of the header) -> {field: whole array}"""
-    km = st["pt"].shape[2]
-    own = ctx is None
-    if own:
-        ctx = Context(grid if grid is not None else P.make_grid(bd, False), km, lib=lib)
-    try:
+    with H.own_or_borrowed(lib, bd, st["pt"].shape[2], ctx, grid) as ctx:
         d = upload(ctx, st)
         call_lib(ctx, d, pr)
         if whole:
             ctx.halo_periodic_group([(d["u_dt"], "A"), (d["v_dt"], "A")])
             ctx.update_dwinds_phys(pr["dt"], d["u_dt"], d["v_dt"], d["u"], d["v"])
         return download(d, st)
-    finally:
-        if own:
-            ctx.close()
 
 
 def run_whole_tile(lib, bd, st, pr):
@@ -158,15 +148,14 @@ def compare(bd, st, got, ref, pr, whole=False):
             continue
         m = written_mask(bd, st, pr, n, whole)
         if n in ("u_dt", "v_dt") and whole:      # the halo update writes their halo
-            m = np.ones(st[n].shape, dtype=bool)
-            bd.view(m, "A", bd.is_, bd.ie, bd.js, bd.je)[...] = False
-            assert np.array_equal(got[n][~m].view(np.uint64), st[n][~m].view(np.uint64)), f"{n}: written on the compute domain"
+            m = H.halo_mask(bd, st[n].shape)
+            assert same_bits(got[n][~m], st[n][~m]), f"{n}: written on the compute domain"
             continue
         if m.any():
             e = P.assert_close(n, got[n][m], ref[n][m], BOUND.get(n, P.TOL))
             if n not in BOUND:
                 worst = max(worst, e)
-        assert np.array_equal(got[n][~m].view(np.uint64), st[n][~m].view(np.uint64)), f"{n}: written outside what the header names"
+        assert same_bits(got[n][~m], st[n][~m]), f"{n}: written outside what the header names"
     return worst
 
 
@@ -236,11 +225,11 @@ def check_checker_against_golden(name):
             if m.any():
                 P.assert_close(n, got[n][m], ref[n][m], BOUND[n])
             continue
-        assert np.array_equal(got[n].view(np.uint64), ref[n].view(np.uint64)), f"{name}: {n} of the restatement is not the reference's, max diff {np.max(np.abs(got[n] - ref[n])):.3e}"
+        assert same_bits(got[n], ref[n]), f"{name}: {n} of the restatement is not the reference's, max diff {np.max(np.abs(got[n] - ref[n])):.3e}"
     # the mask of what the header calls written is the reference's: nothing recorded lies outside it
     for n in OUT:
         m = written_mask(bd, st, pr, n, True)
-        assert np.array_equal(ref[n][~m].view(np.uint64), st[n][~m].view(np.uint64)), f"{name}: the reference writes {n} where the header says nothing is written"
+        assert same_bits(ref[n][~m], st[n][~m]), f"{name}: the reference writes {n} where the header says nothing is written"
     return cnt
 
 
@@ -295,7 +284,7 @@ def check_zero_tendencies(lib, shape, hydrostatic, phys_hydrostatic, nwat=6):
             ulp = np.spacing(np.abs(st[n]))
             assert np.all(np.abs(got[n] - st[n]) <= 2.0 * ulp), "delz moved by more than 2 ulp"
             continue
-        assert np.array_equal(got[n].view(np.uint64), st[n].view(np.uint64)), f"{n}: changed by zero tendencies"
+        assert same_bits(got[n], st[n]), f"{n}: changed by zero tendencies"
     r = (bd.is_, bd.ie, bd.js, bd.je)
     A = lambda a: bd.view(a, "A", *r)      # noqa: E731
     assert np.array_equal(got["u_srf"], A(st["ua"])[:, :, -1]) and np.array_equal(got["v_srf"], A(st["va"])[:, :, -1])
@@ -353,8 +342,7 @@ def check_contract(lib, shape, hydrostatic):
         again = run_lib(lib, bd, st, pr, ctx=ctx, whole=True)
     finally:
         ctx.close()
-    for n in DEVICE:
-        assert np.array_equal(again[n].view(np.uint64), fresh[n].view(np.uint64)), f"{n}: a call after another call differs from a fresh context"
+    H.same_as_fresh_context(DEVICE, fresh, again, "another call")
     return worst
 
 
@@ -364,15 +352,7 @@ def check_refusals(lib):
     ctx = Context(P.make_grid(bd, False), 6, lib=lib)
     try:
         d = upload(ctx, st)
-
-        def refused(match, p=pr, drop=(), **over):
-            dd = dict(d, **{n: None for n in drop})
-            try:
-                call_lib(ctx, dd, p, **over)
-            except Fv3Error as e:
-                assert match in str(e), (match, str(e))
-            else:
-                raise AssertionError(f"fv3_fv_update_phys took a call that must be refused ({match})")
+        refused = H.refusals(functools.partial(call_lib, ctx), d, pr)
 
         for n in ("u_dt", "v_dt", "t_dt", "delp", "pt", "ua", "va", "ps", "pe", "peln", "pk", "u_srf", "v_srf", "q", "qdiag"):
             refused("null", drop=(n,))
@@ -392,9 +372,7 @@ def check_refusals(lib):
         refused("sphum", dict(pr, nwat=0, species={}))      # tau_h2o relaxes q_dt(sphum)
         refused("ak and bk", ak=None)
         refused("ak and bk", bk=None)
-        got = download(d, st)
-        for n in DEVICE:
-            assert np.array_equal(got[n].view(np.uint64), st[n].view(np.uint64)), f"{n}: a refused call wrote"
+        H.assert_nothing_written(d, st, DEVICE)
         # npz < 1 cannot be reached: fv3_create refuses such a domain.  What is NOT refused: nwat > nq without q_dt (nothing is summed),
         # nwat = 1 and 7 (the dry heat capacity of `case default`), the species that the branch does not read left out
         call_lib(ctx, upload(ctx, st), dict(pr, nwat=9, has_qdt=False, species=dict(sphum=1)))
@@ -408,7 +386,6 @@ def check_refusals(lib):
 def check_six_faces(lib, npx=13, npz=6, hydrostatic=False):
     """the six faces as one fv3_group: the bits of face-by-face runs, and ONE merged launch for the column kernel"""
     import cubed_common as CC
-    from gfdl_atmos_cubed_sphere_amd.cubed_dyn import MultiContext
     cs, gs = CC.sphere(npx)
     n = npx - 1
     sts = []
@@ -420,22 +397,7 @@ def check_six_faces(lib, npx=13, npz=6, hydrostatic=False):
     for t, st in enumerate(sts):
         ref, cnt = run_checker(bd, st, pr)
         compare(bd, st, alone[t], ref, pr)
-    mctx = MultiContext([Context(g, npz, lib=lib) for g in gs], group=True)
-    try:
-        assert mctx.group is not None
-        d = {name: mctx.from_host([nonempty(st[name]) for st in sts]) for name in DEVICE}
-        mctx.flush()
-        mctx.group.stats()
-        call_lib(mctx, d, pr)
-        mctx.flush()
-        merged, single = mctx.group.stats()
-        assert merged == 1 and single == 0, f"fv_update_phys of six faces: {merged} merged launches, {single} single ones"
-        for name in DEVICE:
-            got = d[name].download()
-            for t in range(6):
-                assert np.array_equal(got[t].view(np.uint64), alone[t][name].view(np.uint64)), f"face {t + 1} {name}"
-    finally:
-        mctx.close()
+    H.six_faces(lib, gs, npz, sts, DEVICE, lambda mctx, d: call_lib(mctx, d, pr), alone, label="fv_update_phys", host=nonempty)
 
 
 # ---- the Python host: FvDynamics.fv_update_phys ------------------------------------------------------------------------------------
@@ -443,77 +405,36 @@ def check_host(lib, where, gfs_phys=False):
     """FvDynamics.fv_update_phys on the state a step of parity_negadj.run_tile / run_sphere leaves (24 x 16 x 10 on the doubly periodic
     tile, C12 L8, moist, nwat = 6, nq = 7, nonhydrostatic) against the restatement of the column routine, a real exchange of u_dt,
     v_dt as two scalars and the restatement of update_dwinds_phys; with gfs_phys, ua / va against the run's own cubed_to_latlon"""
-    import gfdl_atmos_cubed_sphere_amd.fv_dynamics as M
     import parity_negadj as NA
-    import parity_remap as PR
-    import parity_subgrid as PS
-    from gfdl_atmos_cubed_sphere_amd.layout import periodic_fill
-    orig, kept = M.FvDynamics, {}
     fields = ("u", "v", "w", "delp", "pt", "ua", "va", "q", "delz", "pe", "peln", "pk", "ps")
 
-    class UpFvDynamics(orig):
-        def __init__(self, *a, **kw):
-            super().__init__(*a, **kw)
-            if where == "sphere":      # the tests' gridstructs are the oracle's: what update_dwinds_phys reads comes from there as well
-                import cubed_common as CC
-                cs, _ = CC.sphere(self.ctx.grid.npx)
-                for t, c in enumerate(self.ctx.ctxs):
-                    c.upload_dwinds(PS.oracle_dwinds_geom(cs, t))
+    def call_method(fv, bdt):
+        bd, npz = fv.ctx.bd, fv.ctx.npz
+        tend = []
+        for t, q4 in enumerate(NA._faces(fv.dc.d["q"].download())):
+            rng = np.random.default_rng(960 + t)
+            q = H.compute(bd, q4)
+            f = lambda s: np.asfortranarray(1.0e-3 * rng.standard_normal(s))      # noqa: E731
+            tend.append(dict(t_dt=f((bd.nx, bd.ny, npz)), q_dt=np.asfortranarray(q * rng.uniform(-0.3, 0.3, q.shape) / bdt),
+                             u_dt=f(bd.shape("A", npz)), v_dt=f(bd.shape("A", npz))))
+        pick = (lambda n: tend[0][n]) if len(tend) == 1 else (lambda n: [x[n] for x in tend])
+        fv.fv_update_phys(bdt, pick("t_dt"), pick("q_dt"), pick("u_dt"), pick("v_dt"), phys_hydrostatic=False, gfs_phys=gfs_phys)
+        return dict(tend=tend)
 
-        def step_from_temperature(self, bdt):
-            super().step_from_temperature(bdt)
-            d, bd, npz = self.dc.d, self.ctx.bd, self.ctx.npz
-            dl = lambda n: NA._faces(d[n].download())      # noqa: E731
-            before = {n: [a.copy(order="F") for a in dl(n)] for n in fields}
-            nf = len(before["pt"])
-            tend = []
-            for t in range(nf):
-                rng = np.random.default_rng(960 + t)
-                q = bd.view(before["q"][t], "A", bd.is_, bd.ie, bd.js, bd.je)
-                f = lambda s: np.asfortranarray(1.0e-3 * rng.standard_normal(s))      # noqa: E731
-                tend.append(dict(t_dt=f((bd.nx, bd.ny, npz)), q_dt=np.asfortranarray(q * rng.uniform(-0.3, 0.3, q.shape) / bdt),
-                                 u_dt=f(bd.shape("A", npz)), v_dt=f(bd.shape("A", npz))))
-            pick = (lambda n: tend[0][n]) if nf == 1 else (lambda n: [x[n] for x in tend])
-            self.fv_update_phys(bdt, pick("t_dt"), pick("q_dt"), pick("u_dt"), pick("v_dt"), phys_hydrostatic=False, gfs_phys=gfs_phys)
-            kept.update(before=before, tend=tend, bdt=bdt, consts=dict(self.neg_adj_consts, kappa=self.fl.akap), ptop=self.fl.ptop,
-                        after={n: dl(n) for n in fields + ("u_srf", "v_srf")}, ak=self.ak, bk=self.bk, c2l=self.c2l_ord)
-
-    M.FvDynamics = UpFvDynamics
-    try:
-        base = (NA.run_tile if where == "tile" else NA.run_sphere)(lib)
-    finally:
-        M.FvDynamics = orig
+    base, kept = H.host_step(lib, where, fields, ("u_srf", "v_srf"), call_method)
     bd = base["bd"]
     before, after, tend = kept["before"], kept["after"], kept["tend"]
     nf = len(before["pt"])
-    npz = before["pt"][0].shape[2]
-    sp = {n: PR.MOIST6[n] for n in UI.SPECIES if n != "sphum"}
-    sp["sphum"] = 1
-    nq = before["q"][0].shape[3]
-    pr = dict(dt=kept["bdt"], ptop=kept["ptop"], hydrostatic=False, phys_hydrostatic=False, gfs_phys=gfs_phys, nq=nq, ncnst=nq, nwat=PR.MOIST6["nwat"],
-              species=sp, adjust_mass=np.ones(nq, dtype=np.int32), has_qdt=True, tau_h2o=0.0, ak=kept["ak"], bk=kept["bk"])
+    pr = H.update_phys_params(kept, before["q"][0].shape[3], hydrostatic=False, phys_hydrostatic=False, gfs_phys=gfs_phys)
     ref = []
     for t in range(nf):
         s = {n: before[n][t].copy(order="F") for n in fields}
         s.update({n: tend[t][n].copy(order="F") for n in tend[t]})
-        s.update(qdiag=np.zeros(bd.shape("A", npz) + (0,), order="F"), pkz=np.zeros((bd.nx, bd.ny, npz), order="F"),
-                 u_srf=np.zeros((bd.nx, bd.ny), order="F"), v_srf=np.zeros((bd.nx, bd.ny), order="F"))
-        R.fv_update_phys(bd, npz, pr, s, consts=kept["consts"])
         ref.append(s)
-    if where == "tile":
-        for n in ("u_dt", "v_dt"):
-            periodic_fill(bd, ref[0][n], "A")
-        geoms = [None]
-    else:
-        import cubed_common as CC
-        cs, _ = CC.sphere(base["gs"][0].npx)
-        CC.exchange(cs, ref, ("u_dt", "v_dt"), "A")
-        geoms = [PS.oracle_dwinds_geom(cs, t) for t in range(6)]
+    H.update_phys_reference(where, base, kept, ref, pr)
     worst = 0.0
     r = (bd.is_, bd.ie, bd.js, bd.je)
     for t in range(nf):
-        g = base["g"] if where == "tile" else base["gs"][t]
-        SG.update_dwinds_phys(bd, g.npx, g.npy, g.grid_type, kept["bdt"], ref[t]["u_dt"], ref[t]["v_dt"], ref[t]["u"], ref[t]["v"], geoms[t])
         rows = [("u", "U", (bd.is_, bd.ie, bd.js, bd.je + 1)), ("v", "V", (bd.is_, bd.ie + 1, bd.js, bd.je)), ("pt", "A", r), ("w", "A", r), ("q", "A", r),
                 ("delp", "A", r), ("ps", "A", r)]
         if not gfs_phys:

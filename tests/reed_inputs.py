@@ -18,12 +18,11 @@ decade closer to the poles).
 """
 from __future__ import annotations
 
-import hashlib
-
 import numpy as np
 
 import held_suarez_inputs as HI
 from gfdl_atmos_cubed_sphere_amd.layout import Bounds
+from parity_phys import checksum  # noqa: F401
 
 PI = HI.PI
 # the reference's constants_mod (GFDL defaults) and gfdl_mp_mod's c_liq: what tests/golden/reed_ref/reed_consts.F90 states
@@ -101,14 +100,6 @@ def state(nx, ny, km, seed, zero_tendencies=False, lat_seed=LAT_SEED):
         for n in ("u_dt", "v_dt", "t_dt", "q_dt"):
             st[n][...] = 0.0
     return bd, st
-
-
-def checksum(st):
-    h = hashlib.sha256()
-    for n in sorted(st):
-        h.update(n.encode())
-        h.update(np.ascontiguousarray(st[n]).tobytes())
-    return h.hexdigest()
 
 
 # ---- the recorded cases: 12 x 7 columns; km 1, 2, 12, 32 x (hydrostatic, not) x reed_test 0, 1 x the four flag sets x two pdt x

@@ -13,11 +13,10 @@ columns of their own, 5 K and more below 160 K.
 """
 from __future__ import annotations
 
-import hashlib
-
 import numpy as np
 
 from gfdl_atmos_cubed_sphere_amd.layout import Bounds
+from parity_phys import checksum  # noqa: F401
 
 RDGAS, RVGAS, GRAV, KAPPA = 287.04, 461.50, 9.80, 2.0 / 7.0
 ZVIR = RVGAS / RDGAS - 1.0
@@ -93,14 +92,6 @@ def columns(nx, ny, km, nqa, nwat, seed, ptop=300.0, plant=True):
         pe=pe, peln=np.asfortranarray(np.transpose(peln_c, (0, 2, 1))), pkz=np.asfortranarray(pkz), delz=np.asfortranarray(delz))
     st["planted"] = planted
     return bd, st
-
-
-def checksum(st):
-    h = hashlib.sha256()
-    for n in sorted(st):
-        h.update(n.encode())
-        h.update(np.ascontiguousarray(st[n]).tobytes())
-    return h.hexdigest()
 
 
 def tile_tendencies(nx, ny, npz, seed):

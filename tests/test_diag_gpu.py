@@ -3,14 +3,9 @@ import pytest
 
 import parity_diag as D
 
-from gfdl_atmos_cubed_sphere_amd import lib as L
+from parity_phys import lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return L.load()
 
 
 @pytest.mark.parametrize("in_ng", [0, 3])

@@ -1,22 +1,12 @@
 """fv_diag on the CPU: fv3_interpolate_vertical of the host-emulation library (tests/hostemu) against the outputs of the reference's compiled Fortran
 (tests/golden/diag_interpolate_vertical.npz) and the numpy restatement tests/ref_fv_diag.py, its refusals, the memory contract and the six-face launch.  The same check bodies (tests/parity_diag.py) run on
 the product library in tests/test_diag_gpu.py."""
-import os
-import subprocess
 
 import pytest
 
 import parity_diag as D
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
+from parity_phys import emu  # noqa: F401
 
 
 @pytest.mark.parametrize("in_ng", [0, 3])

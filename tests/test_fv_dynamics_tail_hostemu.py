@@ -3,8 +3,6 @@ against the numpy restatement tests/ref_neg_adj3.py, its properties, and the Pyt
 and cld_amt (fv_dynamics.F90:200-201, :569-572, :658-662, :722-745).  The same cases run on the product library in
 tests/test_fv_dynamics_tail_gpu.py."""
 import functools
-import os
-import subprocess
 
 import pytest
 
@@ -12,15 +10,7 @@ import parity_common as P
 import parity_negadj as NA
 import ref_neg_adj3 as R
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
+from parity_phys import emu  # noqa: F401
 
 
 @functools.lru_cache(maxsize=None)

@@ -2,8 +2,6 @@
 device array between guard bands of 1024 doubles -- the five layouts the kernel reads among them: A x npz with halo, the halo-less
 t_dt / pkz, pe, peln and the latitude planes --, with fresh the outputs prefilled with the pattern, inputs, halos and q_dt
 bit-unchanged, and a call made after an fv3_fv_update_phys in the same context against a fresh context."""
-import os
-import subprocess
 
 import pytest
 
@@ -11,15 +9,7 @@ import held_suarez_inputs as HI
 import memory_contract as MC
 import parity_held_suarez as S
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
+from parity_phys import emu  # noqa: F401
 
 
 @pytest.mark.parametrize("set_name", list(HI.SETS))

@@ -6,16 +6,11 @@ import held_suarez_inputs as HI
 import parity_common as P
 import parity_held_suarez as S
 
-from gfdl_atmos_cubed_sphere_amd import lib as L
+from parity_phys import lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SETS = list(HI.SETS)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return L.load()
 
 
 @pytest.mark.parametrize("set_name", SETS)

@@ -2,8 +2,6 @@
 Fortran (tests/golden/held_suarez_*.npz), and fv3_held_suarez_tend / fv3_age_of_air of the host-emulation library (tests/hostemu) and
 FvDynamics.held_suarez against those outputs, against the restatement at larger shapes, and in their properties.  The same check
 bodies run on the product library in tests/test_held_suarez_gpu.py."""
-import os
-import subprocess
 
 import pytest
 
@@ -11,16 +9,9 @@ import held_suarez_inputs as HI
 import parity_common as P
 import parity_held_suarez as S
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
+from parity_phys import emu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SETS = list(HI.SETS)
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
 
 
 @pytest.mark.parametrize("name", list(HI.CASES))

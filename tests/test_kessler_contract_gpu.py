@@ -5,15 +5,10 @@ import kessler_inputs as KI
 import memory_contract as MC
 import parity_kessler as S
 
-from gfdl_atmos_cubed_sphere_amd import lib as L
 from test_kessler_contract_hostemu import IDS, SHAPES
+from parity_phys import lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return L.load()
 
 
 @pytest.mark.parametrize("flags", list(KI.FLAGS))

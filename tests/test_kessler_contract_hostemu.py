@@ -4,8 +4,6 @@ pe, peln, pk, ps, rain -- and the twelve planes that hold a column's state betwe
 of their own and filled with the pattern at the head of every call: written by the first cycle before a later one reads them; rain
 prefilled with the pattern and written in every cell; halos and the other tracer planes bit-unchanged; calls made after an
 fv3_fv_update_phys, a call without work planes (K_cycle = 1) and another instantiation in the same context against a fresh context."""
-import os
-import subprocess
 
 import pytest
 
@@ -13,17 +11,10 @@ import kessler_inputs as KI
 import memory_contract as MC
 import parity_kessler as S
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
+from parity_phys import emu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SHAPES = ((21, 7, 1), (21, 7, 2), (37, 21, 12))
 IDS = ["21x7x1", "21x7x2", "37x21x12"]
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
 
 
 @pytest.mark.parametrize("flags", list(KI.FLAGS))

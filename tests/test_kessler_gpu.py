@@ -5,16 +5,11 @@ import pytest
 import kessler_inputs as KI
 import parity_kessler as S
 
-from gfdl_atmos_cubed_sphere_amd import lib as L
+from parity_phys import lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FLAGS = list(KI.FLAGS)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return L.load()
 
 
 @pytest.mark.parametrize("flags", FLAGS)

@@ -2,8 +2,6 @@
 compiled Fortran (tests/golden/kessler/*.npz), and fv3_k_warm_rain / fv3_qs_wat_init of the host-emulation library (tests/hostemu) and
 FvDynamics.k_warm_rain against those outputs, against the restatement at a shape with several blocks and a tail block, and in their
 properties.  The same check bodies run on the product library in tests/test_kessler_gpu.py."""
-import os
-import subprocess
 
 import pytest
 
@@ -11,17 +9,10 @@ import kessler_inputs as KI
 import parity_kessler as S
 import ref_kessler as R
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
+from parity_phys import emu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 FLAGS = list(KI.FLAGS)
 KMS = (1, 2, 12, 32)
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
 
 
 def cases_of(km, flags):

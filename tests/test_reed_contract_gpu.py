@@ -6,15 +6,10 @@ import memory_contract as MC
 import parity_reed as S
 import reed_inputs as RI
 
-from gfdl_atmos_cubed_sphere_amd import lib as L
 from test_reed_contract_hostemu import IDS, SHAPES
+from parity_phys import lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return L.load()
 
 
 @pytest.mark.parametrize("flags", list(RI.FLAGS))

@@ -4,8 +4,6 @@ q_dt / delz, pe, peln, phis, rain -- and the six coefficient planes of the bound
 bands of their own and filled with the pattern at the head of every call; with fresh the outputs prefilled with the pattern; inputs
 and halos bit-unchanged; calls made after an fv3_fv_update_phys, a terminator call and another branch set in the same context against
 a fresh context."""
-import os
-import subprocess
 
 import pytest
 
@@ -13,17 +11,10 @@ import memory_contract as MC
 import parity_reed as S
 import reed_inputs as RI
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
+from parity_phys import emu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SHAPES = ((21, 7, 1), (21, 7, 2), (37, 21, 12))
 IDS = ["21x7x1", "21x7x2", "37x21x12"]
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
 
 
 @pytest.mark.parametrize("flags", list(RI.FLAGS))

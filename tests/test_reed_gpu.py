@@ -6,16 +6,11 @@ import parity_common as P
 import parity_reed as S
 import reed_inputs as RI
 
-from gfdl_atmos_cubed_sphere_amd import lib as L
+from parity_phys import lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FLAGS = list(RI.FLAGS)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return L.load()
 
 
 @pytest.mark.parametrize("flags", FLAGS)

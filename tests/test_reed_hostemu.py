@@ -3,8 +3,6 @@ outputs of the reference's compiled Fortran (tests/golden/reed/*.npz), and fv3_r
 host-emulation library (tests/hostemu) and FvDynamics.reed_sim_phys against those outputs, against the restatement at shapes with
 several blocks and a tail block, and in their properties.  The same check bodies run on the product library in
 tests/test_reed_gpu.py."""
-import os
-import subprocess
 
 import pytest
 
@@ -12,16 +10,9 @@ import parity_common as P
 import parity_reed as S
 import reed_inputs as RI
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
+from parity_phys import emu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 FLAGS = list(RI.FLAGS)
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
 
 
 def cases_of(group):

@@ -1,8 +1,6 @@
 """The memory contract of fv3_fv_subgrid_z and fv3_update_dwinds_phys on the CPU (tests/memory_contract.py): FV3_MI355X_POISON=1, every
 device array between guard bands, the outputs u_dt / v_dt prefilled with the pattern, halos / levels below kbot / tracers beyond nq
 bit-unchanged, and a call made after another kind of call in the same context against a fresh context."""
-import os
-import subprocess
 
 import pytest
 
@@ -10,15 +8,7 @@ import memory_contract as MC
 import parity_common as P
 import parity_subgrid as S
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
+from parity_phys import emu  # noqa: F401
 
 
 @pytest.mark.parametrize("hydrostatic", [False, True], ids=["nh", "hydro"])

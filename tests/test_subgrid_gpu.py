@@ -5,14 +5,9 @@ import parity_common as P
 import parity_subgrid as S
 import subgrid_inputs as SI
 
-from gfdl_atmos_cubed_sphere_amd import lib as L
+from parity_phys import lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return L.load()
 
 
 def test_library_against_the_compiled_reference(lib):

@@ -2,8 +2,6 @@
 (tests/golden/subgrid_*.npz), and fv3_fv_subgrid_z / fv3_update_dwinds_phys of the host-emulation library (tests/hostemu) against
 those outputs, against the restatement at larger shapes, and in their properties.  The same check bodies run on the product library
 in tests/test_subgrid_gpu.py."""
-import os
-import subprocess
 
 import pytest
 
@@ -11,15 +9,7 @@ import parity_common as P
 import parity_subgrid as S
 import subgrid_inputs as SI
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
+from parity_phys import emu  # noqa: F401
 
 
 @pytest.mark.parametrize("name", list(SI.SG_CASES))

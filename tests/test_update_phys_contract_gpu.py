@@ -6,14 +6,9 @@ import memory_contract as MC
 import parity_common as P
 import parity_update_phys as S
 
-from gfdl_atmos_cubed_sphere_amd import lib as L
+from parity_phys import lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return L.load()
 
 
 @pytest.mark.parametrize("hydrostatic", [False, True], ids=["nh", "hydro"])

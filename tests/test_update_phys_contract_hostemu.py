@@ -2,8 +2,6 @@
 every device array between guard bands -- the halo-less t_dt / q_dt and the three pressure layouts among them --, the pure outputs
 prefilled with the pattern, halos and everything the header calls unwritten bit-unchanged, and a call made after other kinds of
 call in the same context against a fresh context."""
-import os
-import subprocess
 
 import pytest
 
@@ -11,15 +9,7 @@ import memory_contract as MC
 import parity_common as P
 import parity_update_phys as S
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
+from parity_phys import emu  # noqa: F401
 
 
 @pytest.mark.parametrize("hydrostatic", [False, True], ids=["nh", "hydro"])

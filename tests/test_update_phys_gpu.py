@@ -6,18 +6,13 @@ import parity_common as P
 import parity_update_phys as S
 import update_phys_inputs as UI
 
-from gfdl_atmos_cubed_sphere_amd import lib as L
+from parity_phys import lib  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 IDS = ["21x7x1", "21x7x2", "40x19x12", "130x100x5"]
 MODES = [(True, True), (False, True), (False, False)]      # (hydrostatic, phys_hydrostatic)
 MODE_IDS = ["hydro", "nh_phys_hydro", "nh"]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return L.load()
 
 
 def test_library_against_the_compiled_reference(lib):

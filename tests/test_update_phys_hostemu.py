@@ -2,8 +2,6 @@
 (tests/golden/update_phys_*.npz), and fv3_fv_update_phys of the host-emulation library (tests/hostemu) with the sequence behind it
 against those outputs, against the restatement at larger shapes, and in its properties.  The same check bodies run on the product
 library in tests/test_update_phys_gpu.py."""
-import os
-import subprocess
 
 import pytest
 
@@ -11,18 +9,11 @@ import parity_common as P
 import parity_update_phys as S
 import update_phys_inputs as UI
 
-from gfdl_atmos_cubed_sphere_amd.lib import Fv3Lib
+from parity_phys import emu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 IDS = ["21x7x1", "21x7x2", "40x19x12", "130x100x5"]
 MODES = [(True, True), (False, True), (False, False)]      # (hydrostatic, phys_hydrostatic)
 MODE_IDS = ["hydro", "nh_phys_hydro", "nh"]
-
-
-@pytest.fixture(scope="module")
-def emu():
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hostemu"), "-s"])
-    return Fv3Lib(os.path.join(HERE, "hostemu", "libfv3_hostemu.so"))
 
 
 @pytest.mark.parametrize("name", list(UI.CASES))

@@ -15,11 +15,10 @@ Planted, each in cells of its own, so that the recorded cases and the larger sha
 """
 from __future__ import annotations
 
-import hashlib
-
 import numpy as np
 
 from gfdl_atmos_cubed_sphere_amd.layout import Bounds
+from parity_phys import checksum  # noqa: F401
 
 RDGAS, RVGAS, GRAV, KAPPA = 287.04, 461.50, 9.80, 2.0 / 7.0
 CP_AIR = RDGAS / KAPPA
@@ -120,14 +119,6 @@ def state(nx, ny, km, nq, ncnst, nwat, seed, ptop=300.0, zero_tendencies=False):
         for n in ("t_dt", "q_dt", "u_dt", "v_dt"):
             st[n][...] = 0.0
     return bd, st
-
-
-def checksum(st):
-    h = hashlib.sha256()
-    for n in sorted(st):
-        h.update(n.encode())
-        h.update(np.ascontiguousarray(st[n]).tobytes())
-    return h.hexdigest()
 
 
 # ---- the recorded cases: 6 x 4 columns (an interior of 4 x 2 inside the one ring update_dwinds_phys reads), 8 levels, nq = 8 of
