@@ -62,9 +62,7 @@ class CubeHalo:
                 cols[4].append(tb["sign"] if vector else np.ones(n, dtype=np.int64))
         arrs = [np.ascontiguousarray(np.concatenate(c), dtype=np.int32) for c in cols]
         h = _vp()
-        ip = C.POINTER(C.c_int)
-        self.lib.check(self.lib.dll.fv3_gather_create(self.ctx.h, C.c_int(arrs[0].size), *[a.ctypes.data_as(ip) for a in arrs],
-                                                     C.byref(h)), "fv3_gather_create")
+        self.ctx.call("fv3_gather_create", arrs[0].size, *[a.ctypes for a in arrs], C.byref(h))
         self._handles[key] = h
         return h
 
@@ -82,12 +80,12 @@ class CubeHalo:
         sarr = (C.c_size_t * n)(*strides)
         handle = self._handle(kind, vector)
         self._fan_in()
-        self.lib.check(self.lib.dll.fv3_gather_run(self.ctx.h, handle, C.c_int(nk), C.c_int(n), parr, sarr), "fv3_gather_run")
+        self.ctx.call("fv3_gather_run", handle, nk, n, parr, sarr)
         self._fan_out()
 
     def close(self):
         for h in self._handles.values():
-            self.lib.dll.fv3_gather_destroy(h)
+            self.lib.call("fv3_gather_destroy", h)
         self._handles = {}
 
 
@@ -148,13 +146,11 @@ class CubeHaloRank:
                 unpack[4].append(np.ones(n, dtype=np.int64))
                 pos += n
             n_recv.append(pos)
-        ip = C.POINTER(C.c_int)
 
         def make(cols):
             arrs = [np.ascontiguousarray(np.concatenate(c), dtype=np.int32) for c in cols]
             h = _vp()
-            self.lib.check(self.lib.dll.fv3_gather_create(self.ctx.h, C.c_int(arrs[0].size), *[a.ctypes.data_as(ip) for a in arrs],
-                                                         C.byref(h)), "fv3_gather_create")
+            self.ctx.call("fv3_gather_create", arrs[0].size, *[a.ctypes for a in arrs], C.byref(h))
             return h
         plan = dict(peers=peers, n_send=n_send, n_recv=n_recv, pack=make(pack), unpack=make(unpack))
         self._plans[key] = plan
@@ -184,8 +180,7 @@ class CubeHaloRank:
         ptrs = [f.ptr for f in fields] + [0] * (self.SLOT0 - len(fields)) + [b.ptr for b in bufs]
         strides = [int(f.shape[0] * f.shape[1]) for f in fields] + [0] * (self.SLOT0 - len(fields)) + [int(n) for n in lens]
         n = len(ptrs)
-        self.lib.check(self.lib.dll.fv3_gather_run(self.ctx.h, handle, C.c_int(nk), C.c_int(n), (C.c_void_p * n)(*ptrs),
-                                                   (C.c_size_t * n)(*strides)), "fv3_gather_run")
+        self.ctx.call("fv3_gather_run", handle, nk, n, (C.c_void_p * n)(*ptrs), (C.c_size_t * n)(*strides))
 
     # ---- the update -------------------------------------------------------------------------------------------------------
     def start(self, kind: str, fields, vector: bool = True):
@@ -234,8 +229,8 @@ class CubeHaloRank:
 
     def close(self):
         for p in self._plans.values():
-            self.lib.dll.fv3_gather_destroy(p["pack"])
-            self.lib.dll.fv3_gather_destroy(p["unpack"])
+            self.lib.call("fv3_gather_destroy", p["pack"])
+            self.lib.call("fv3_gather_destroy", p["unpack"])
         self._plans = {}
 
 

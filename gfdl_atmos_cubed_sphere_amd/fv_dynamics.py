@@ -35,10 +35,8 @@ class _TracerView:
     """one tracer (A x npz) of a tracer array on the device, for the entry points that take a field"""
 
     def __init__(self, q, iq: int):
-        import ctypes as C
         self.shape = tuple(q.shape[:3])
-        self.ptr = q.ptr + 8 * int(np.prod(self.shape)) * iq
-        self.p = C.cast(C.c_void_p(self.ptr), C.POINTER(C.c_double))
+        self.ptr = self._as_parameter_ = q.ptr + 8 * int(np.prod(self.shape)) * iq
 
 
 class FvDynamics:
@@ -397,12 +395,10 @@ class FvDynamics:
 
     def _carry_unadvected(self, dst, src):
         """the last dnats tracers from one buffer of the tracer ping-pong pair to the other: tracer_2d leaves them where they were"""
-        import ctypes as C
         nadv = self.nq - self.dnats
         for a, b in zip(getattr(dst, "a", [dst]), getattr(src, "a", [src])):
             n3 = int(np.prod(a.shape[:3]))
-            a.ctx.lib.check(a.ctx.lib.dll.fv3_memcpy_d2d(a.ctx.h, C.c_void_p(a.ptr + 8 * n3 * nadv), C.c_void_p(b.ptr + 8 * n3 * nadv),
-                                                         C.c_size_t(8 * n3 * self.dnats)), "fv3_memcpy_d2d")
+            a.ctx.call("fv3_memcpy_d2d", a.ptr + 8 * n3 * nadv, b.ptr + 8 * n3 * nadv, 8 * n3 * self.dnats)
 
     # -- consv_am -------------------------------------------------------------------------------------------------
     def _aam(self, aam_name: str, ps_name: str):
